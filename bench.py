@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """Flagship serving benchmark — the driver contract.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+                    [--full]
 
 Measures the BASELINE.json headline: predict req/sec (whole node) plus
-p50 cold-load latency. One rank per GPU (the driver launches ranks via
+p50 cold-load latency. A plain run does only what that figure needs:
+set up, warm up, time the K steps, print one JSON result line. --full
+adds the secondary measurements that take runs of their own (today:
+the headline's warm-cache req/sec half). --dump-outputs DIR writes the
+responses of the last timed step as DIR/<output name>.npy (one row per
+request, in request order) so two builds can be compared output for
+output; inputs and the request schedule are seeded. One rank per GPU (the driver launches ranks via
 torch.distributed.run for N>1); each rank runs the full node-local
 serving stack — disk model repo -> DiskModelProvider -> byte-budget LRU
 -> GPU model pool (CDNA4 HIP engine, bf16) — and drives it with
@@ -17,9 +24,10 @@ Modes (--mode):
         hardlinked ResNet-50 models, per-GPU pool capped at 10, Zipf-1.1
         access, served over the NATIVE socket front-end (real gRPC over
         TCP loopback). Emits BOTH metric halves: LRU predict req/sec
-        (the timed region) and p50 cold-load latency, plus a warm-cache
-        req/sec measured separately BEFORE the timed region. With
-        world>1 it becomes the ring workload (configs[3]): ownership by
+        (the timed region) and p50 cold-load latency; with --full also
+        a warm-cache req/sec measured separately BEFORE the timed
+        region. With world>1 it becomes the ring workload
+        (configs[3]): ownership by
         consistent hash over ranks, replicas=2, replica fan-out over
         the RCCL/xGMI plane at preload.
   warm  ResNet-50 warm-cache predict loop (BASELINE configs[1])
@@ -300,6 +308,53 @@ def _graph_status(pool):
     return None
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def _dump_outputs(out_dir, captured, transport, rank, world) -> None:
+    """Write the captured responses of the last timed step: one
+    DIR/<output name>.npy per response tensor, rows in request order.
+    Rank r>0 of a multi-rank run writes <output name>.rank<r>.npy."""
+    from tfservingcache_amd.wire.tensor import tensorproto_to_numpy
+    per_name = {}
+    for i in sorted(captured):
+        resp = captured[i]
+        if transport == "native-rest":
+            body = json.loads(resp)
+            if "predictions" in body:
+                outs = {"predictions": np.asarray(body["predictions"])}
+            else:
+                outs = body["outputs"]
+                if not isinstance(outs, dict):
+                    outs = {"outputs": outs}
+                outs = {k: np.asarray(v) for k, v in outs.items()}
+        else:
+            if isinstance(resp, (bytes, bytearray, memoryview)):
+                resp = m.PredictResponse.decode(bytes(resp))
+            outs = {k: tensorproto_to_numpy(tp)
+                    for k, tp in resp.outputs.items()}
+        for k, v in outs.items():
+            per_name.setdefault(k, []).append(v)
+    if not per_name:
+        raise SystemExit("--dump-outputs: the last timed step returned "
+                         "no responses")
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES_MAX // len(per_name)
+    for k in sorted(per_name):
+        arr = np.stack(per_name[k])
+        if arr.dtype != np.float64:
+            arr = arr.astype(np.float32)
+        if arr.nbytes > budget:
+            # fixed, seeded sample of the flattened tensor
+            idx = np.sort(np.random.default_rng(0).integers(
+                0, arr.size, budget // arr.itemsize))
+            arr = arr.reshape(-1)[idx]
+        safe = "".join(c if c.isalnum() or c in "-_." else "_" for c in k)
+        if world > 1 and rank > 0:
+            safe += f".rank{rank}"
+        np.save(os.path.join(out_dir, safe + ".npy"), arr)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -361,7 +416,23 @@ def main() -> int:
                          "loopback (registered Predicts bypass Python); "
                          "native-rest: C++ HTTP/1.1 JSON front-end over "
                          "TCP loopback")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements that need "
+                         "runs of their own (headline: the warm-cache "
+                         "req/sec half); off by default so a plain run "
+                         "only times the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the responses of "
+                         "the LAST timed step as DIR/<output name>.npy "
+                         "(float32/float64, one row per request in "
+                         "request order; a fixed seeded sample when "
+                         "over 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and args.client_procs > 0:
+        raise SystemExit("--dump-outputs needs in-process clients "
+                         "(drop --client-procs)")
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -529,14 +600,18 @@ def main() -> int:
     lat_lock = threading.Lock()
     latencies = []          # per-request wall seconds (timed section)
     timing_on = [False]
+    capture_on = [False]    # --dump-outputs: keep the last step's replies
+    captured = {}           # request index -> raw response
 
     def timed(fn):
         def run(i):
             t0 = time.monotonic()
-            fn(i)
+            resp = fn(i)
             if timing_on[0]:
                 with lat_lock:
                     latencies.append(time.monotonic() - t0)
+            if capture_on[0]:
+                captured[i] = resp
         return run
 
     grpc_server = None
@@ -584,7 +659,7 @@ def main() -> int:
 
         tl = threading_mod.local()
 
-        def _rest_call(name: str) -> None:
+        def _rest_call(name: str) -> bytes:
             sock = getattr(tl, "sock", None)
             if sock is None:
                 sock = socket_mod.create_connection(
@@ -616,9 +691,10 @@ def main() -> int:
                 raise RuntimeError(
                     f"rest predict failed: {status} "
                     f"{rest[:200].decode(errors='replace')}")
+            return rest[:clen]
 
-        def one_request(i: int) -> None:
-            _rest_call(pick(i))
+        def one_request(i: int):
+            return _rest_call(pick(i))
     elif args.transport in ("grpc", "native"):
         import grpc as grpc_mod
         if args.transport == "native":
@@ -661,11 +737,11 @@ def main() -> int:
                 request_serializer=lambda b: b,
                 response_deserializer=m.PredictResponse.decode))
 
-        def one_request(i: int) -> None:
-            rpcs[i % len(rpcs)](req_cache[pick(i)], timeout=300)
+        def one_request(i: int):
+            return rpcs[i % len(rpcs)](req_cache[pick(i)], timeout=300)
     else:
-        def one_request(i: int) -> None:
-            handler.predict_bytes(req_cache[pick(i)])
+        def one_request(i: int):
+            return handler.predict_bytes(req_cache[pick(i)])
 
     one_request = timed(one_request)
 
@@ -676,10 +752,10 @@ def main() -> int:
 
     pool_executor = ThreadPoolExecutor(max_workers=args.threads)
 
-    # headline: measure the WARM-cache half first (one resident model,
-    # same transport), strictly outside the LRU timed region
+    # headline --full: measure the WARM-cache half first (one resident
+    # model, same transport), strictly outside the LRU timed region
     warm_req_per_sec = None
-    if headline:
+    if headline and args.full:
         if args.transport == "native-rest":
             def warm_one(i: int) -> None:
                 _rest_call(warm_name)
@@ -754,8 +830,11 @@ def main() -> int:
     timing_on[0] = True
     t_start = time.monotonic()
     for k in range(args.steps):
+        if args.dump_outputs and k == args.steps - 1:
+            capture_on[0] = True
         step((args.warmup + k) * REQS_PER_STEP)
     timing_on[0] = False
+    capture_on[0] = False
     barrier_sync()
     elapsed = time.monotonic() - t_start
 
@@ -797,6 +876,10 @@ def main() -> int:
         pass
     stages = {k: round(v / 1e9, 3) for k, v in stages.items()}
 
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, captured, args.transport,
+                      rank, world)
+
     if rank == 0:
         result = {
             "metric": "predict req/sec (whole node)",
@@ -823,6 +906,7 @@ def main() -> int:
                                 if eff_mode == "ring" else ""),
                 "mode": (f"headline ({eff_mode})" if headline
                          else args.mode),
+                "full": bool(args.full),
                 "warm_req_per_sec": (round(warm_req_per_sec, 2)
                                      if warm_req_per_sec else None),
                 "warm_images_per_sec": (
