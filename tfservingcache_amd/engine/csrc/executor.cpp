@@ -142,11 +142,20 @@ static void launch_call(const Call& c, hipStream_t s) {
     case K_PAD_LAST:
       launch_pad_last(s, cp(0), p(1), I[0], int(I[1]), int(I[2]));
       break;
-    case K_ATTENTION:
-      // ptrs: [q, k, v, out]; ints: [B, S, H, D]; floats: [scale]
+    case K_ATTENTION: {
+      // ptrs: [q, k, v, out, bias|0]; ints: [B, S, H, D, sb, sh, sq];
+      // floats: [scale]. The 4-pointer / 4-int form (no bias) stays
+      // valid; bias strides are in elements, 0 = broadcast.
+      const ushort* abias =
+          c.ptrs.size() > 4 && c.ptrs[4] ? cp(4) : nullptr;
+      if (abias && I.size() < 7)
+        throw std::runtime_error("attention bias needs [sb, sh, sq]");
       launch_attention(s, cp(0), cp(1), cp(2), p(3), int(I[0]), int(I[1]),
-                       int(I[2]), int(I[3]), c.floats[0]);
+                       int(I[2]), int(I[3]), c.floats[0], abias,
+                       abias ? I[4] : 0, abias ? I[5] : 0,
+                       abias ? I[6] : 0);
       break;
+    }
     case K_GEMM_FP8: {
       // ptrs: [Aq, sa, Bq, sb, bias|0, residual|0, C]
       // ints: [M, N, Kp, act]

@@ -148,8 +148,15 @@ void launch_quant_rowwise(hipStream_t s, const ushort* x, uint8_t* q,
 
 // Fused multi-head attention over the natural [B*S, H*D] QKV layout
 // (flash-style online softmax; D must be 64). See ops/attention.hip.
+// bias (nullable, bf16) is added to the scaled scores before the
+// softmax, read as bias[b*sb + h*sh + q*sq + kv] with strides in
+// elements; a 0 stride broadcasts that dimension ([B,1,1,S] key
+// padding: sb=S; [1,1,S,S] causal: sq=S). A null bias launches the
+// unmasked kernels.
 void launch_attention(hipStream_t s, const ushort* Q, const ushort* K,
                       const ushort* V, ushort* O, int B, int S, int H,
-                      int D_, float scale);
+                      int D_, float scale, const ushort* bias = nullptr,
+                      int64_t bias_sb = 0, int64_t bias_sh = 0,
+                      int64_t bias_sq = 0);
 
 }  // namespace tfsc

@@ -18,9 +18,25 @@
 // region overlaps the (dead after the prologue) Q tile. 80 KB LDS ->
 // 2 workgroups/CU. Requires head_dim D == 64 (BERT-base class); the
 // planner keeps the unfused path otherwise.
+//
+// Optional additive bias (HAS_BIAS): the attention-mask term real
+// exports add to the scaled scores before the softmax,
+//
+//   score[b,h,q,kv] = scale * q.k + bias[b*sb + h*sh + q*sq + kv]
+//
+// bf16, strides in elements, stride 0 = broadcast: [B,1,1,S] key
+// padding (sb=S), [1,1,S,S] causal constant (sq=S), [B,1,S,S],
+// [B,H,S,S]. The bias is read straight from global memory into the
+// score-fragment lanes (kv column = lane&15, q rows = (lane>>4)*4+r)
+// BEFORE the QK^T MFMA block so the load latency hides under it; no
+// LDS. Indices are clamped to S-1 on both axes, so no read leaves the
+// operand. -inf entries behave exactly like absent keys; a row with
+// every key at -inf yields zeros. The HAS_BIAS=false instantiations are
+// the unmasked kernels, unchanged.
 #include "../common.h"
 #include "../kernels.h"
 
+#include <climits>
 #include <stdexcept>
 
 namespace tfsc {
@@ -29,6 +45,7 @@ namespace attn {
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
+using ushort2_t = __attribute__((ext_vector_type(2))) ushort;
 
 constexpr int D = 64;          // head dim
 constexpr int QBLK = 64;       // q rows per workgroup (16 per wave)
@@ -94,13 +111,15 @@ TFSC_DEV void stage_vt(const ushort* __restrict__ src, int64_t ld,
 // RING = staged kv-tile slots: 4 (pair prefetch, 80 KB LDS, 2 WG/CU)
 // for long sequences; 2 (no prefetch needed when n_kv <= 2, 48 KB LDS,
 // 3 WG/CU) for the S <= 128 serving shapes
-template <int RING>
+template <int RING, bool HAS_BIAS>
 __global__ __launch_bounds__(THREADS)
 void attention_kernel(const ushort* __restrict__ Q,
                       const ushort* __restrict__ K,
                       const ushort* __restrict__ V,
                       ushort* __restrict__ O,
-                      int B, int S, int H, float scale, int n_qblk) {
+                      int B, int S, int H, float scale, int n_qblk,
+                      const ushort* __restrict__ bias, int64_t bias_sb,
+                      int64_t bias_sh, int bias_sq) {
   // LDS: K ring RINGx8KB | V^T ring RINGx8KB | q/p overlay 16 KB
   // (q tile uses the first 8 KB until its registers are loaded; the
   // per-wave [16][128] P bounce then reuses the whole 16 KB)
@@ -149,12 +168,32 @@ void attention_kernel(const ushort* __restrict__ Q,
   __syncthreads();   // q_lds consumed; the region becomes the P bounce
 
   // ---- online softmax state: this lane covers rows wave*16 + kgrp*4+r
+  // With a bias a whole tile pair of a row can sit at -inf (masked
+  // keys) or -3.0e38 (kv tail); the running max then starts ABOVE the
+  // tail sentinel so those columns exponentiate to 0, not exp(0).
   float m_run[4], l_run[4];
   f32x4_t o_acc[4] = {};      // O fragments over d (4 x 16 cols)
   #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    m_run[r] = -3.0e38f;
+    m_run[r] = HAS_BIAS ? -1.0e38f : -3.0e38f;
     l_run[r] = 0.f;
+  }
+
+  // bias rows of this lane: q rows past S clamp to S-1 (the epilogue
+  // drops them); a 0 stride reads the one broadcast row
+  // (32-bit unsigned byte offsets from the wave-uniform (b, h) plane:
+  // one VGPR per address; the launcher bounds the plane to 2^31)
+  const char* bias_bh = nullptr;
+  uint32_t bias_roff[4] = {};
+  if (HAS_BIAS) {
+    bias_bh = reinterpret_cast<const char*>(
+        bias + (int64_t)b * bias_sb + (int64_t)h * bias_sh);
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int qrow = q0 + wave * 16 + kgrp * 4 + r;
+      qrow = qrow < S ? qrow : S - 1;
+      bias_roff[r] = uint32_t(qrow) * uint32_t(bias_sq) * 2u;
+    }
   }
 
   const int n_kv = (S + KVBLK - 1) / KVBLK;
@@ -165,6 +204,42 @@ void attention_kernel(const ushort* __restrict__ Q,
     // barrier here covers the pair t prefetch issued in iteration t-1
     if (t > 0) __syncthreads();
     const int base = RING >= 4 ? (t & 1) * 2 : 0;  // slots of this pair
+    const int kv_base = t * 2 * KVBLK;
+    // bias for this lane's 8 kv columns x 4 q rows, issued ahead of
+    // the MFMA block so the latency hides under it — and ahead of the
+    // next pair's prefetch: vector loads retire in order, so behind it
+    // the first use of the bias would wait for the prefetch too. kv
+    // columns past S clamp to S-1 (masked below). A per-key bias
+    // (sq == 0) is one load per column, shared by the lane's 4 q rows;
+    // a per-query bias is 32. Columns ni and ni+4 share a register as
+    // two bf16 halves: 16 VGPRs, not 32, keeps the S <= 128 variant at
+    // 3 workgroups per CU. The sq branch is wave-uniform.
+    ushort2_t bv[4][4] = {};
+    if (HAS_BIAS) {
+      uint32_t off[8];
+      #pragma unroll
+      for (int ni = 0; ni < 8; ++ni) {
+        int kv_col = kv_base + ni * 16 + frow;
+        off[ni] = uint32_t(kv_col < S ? kv_col : S - 1) * 2u;
+      }
+      if (bias_sq == 0) {
+        ushort bk[8];
+        #pragma unroll
+        for (int ni = 0; ni < 8; ++ni)
+          bk[ni] = *reinterpret_cast<const ushort*>(bias_bh + off[ni]);
+        #pragma unroll
+        for (int ni = 0; ni < 8; ++ni)
+          #pragma unroll
+          for (int r = 0; r < 4; ++r) bv[ni & 3][r][ni >> 2] = bk[ni];
+      } else {
+        #pragma unroll
+        for (int ni = 0; ni < 8; ++ni)
+          #pragma unroll
+          for (int r = 0; r < 4; ++r)
+            bv[ni & 3][r][ni >> 2] = *reinterpret_cast<const ushort*>(
+                bias_bh + (bias_roff[r] + off[ni]));
+      }
+    }
     if (RING >= 4 && t + 1 < n_pair) {
       const int nb = ((t + 1) & 1) * 2;
       stage_rows_glds(Kb, ld, (2 * t + 2) * KVBLK, S - 1, k_lds(nb),
@@ -193,15 +268,17 @@ void attention_kernel(const ushort* __restrict__ Q,
         }
       }
     }
-    // scale + mask the kv tail
-    const int kv_base = t * 2 * KVBLK;
+    // scale (+ bias) + mask the kv tail
     #pragma unroll
     for (int ni = 0; ni < 8; ++ni) {
       int kv_col = kv_base + ni * 16 + frow;   // this lane's kv column
       bool valid = kv_col < S;
       #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        sc[ni][r] = valid ? sc[ni][r] * scale : -3.0e38f;
+      for (int r = 0; r < 4; ++r) {
+        float v = sc[ni][r] * scale;
+        if (HAS_BIAS) v += bf2f(bv[ni & 3][r][ni >> 2]);
+        sc[ni][r] = valid ? v : -3.0e38f;
+      }
     }
 
     // ---- per-row max over the 128 kv columns (one pass per pair)
@@ -295,19 +372,38 @@ void attention_kernel(const ushort* __restrict__ Q,
 
 void launch_attention(hipStream_t s, const ushort* Q, const ushort* K,
                       const ushort* V, ushort* O, int B, int S, int H,
-                      int D_, float scale) {
+                      int D_, float scale, const ushort* bias,
+                      int64_t bias_sb, int64_t bias_sh, int64_t bias_sq) {
   if (D_ != attn::D)
     throw std::runtime_error("fused attention requires head_dim == 64");
+  // the kernel indexes one (b, h) bias plane with 32-bit offsets
+  if (bias && (bias_sb < 0 || bias_sh < 0 || bias_sq < 0 ||
+               (int64_t)(S - 1) * bias_sq + S > INT32_MAX))
+    throw std::runtime_error("fused attention: bad bias strides");
   int n_qblk = (S + attn::QBLK - 1) / attn::QBLK;
   dim3 grid(B * H * n_qblk);
-  if (S <= 2 * attn::KVBLK)
-    hipLaunchKernelGGL(attn::attention_kernel<2>, grid,
-                       dim3(attn::THREADS), 0, s, Q, K, V, O, B, S, H,
-                       scale, n_qblk);
-  else
-    hipLaunchKernelGGL(attn::attention_kernel<4>, grid,
-                       dim3(attn::THREADS), 0, s, Q, K, V, O, B, S, H,
-                       scale, n_qblk);
+  dim3 block(attn::THREADS);
+  const bool small = S <= 2 * attn::KVBLK;
+  const int sq = int(bias_sq);
+  if (!bias) {
+    // unmasked models: the same two instantiations as ever
+    if (small)
+      hipLaunchKernelGGL((attn::attention_kernel<2, false>), grid, block,
+                         0, s, Q, K, V, O, B, S, H, scale, n_qblk,
+                         nullptr, 0, 0, 0);
+    else
+      hipLaunchKernelGGL((attn::attention_kernel<4, false>), grid, block,
+                         0, s, Q, K, V, O, B, S, H, scale, n_qblk,
+                         nullptr, 0, 0, 0);
+  } else if (small) {
+    hipLaunchKernelGGL((attn::attention_kernel<2, true>), grid, block, 0,
+                       s, Q, K, V, O, B, S, H, scale, n_qblk, bias,
+                       bias_sb, bias_sh, sq);
+  } else {
+    hipLaunchKernelGGL((attn::attention_kernel<4, true>), grid, block, 0,
+                       s, Q, K, V, O, B, S, H, scale, n_qblk, bias,
+                       bias_sb, bias_sh, sq);
+  }
 }
 
 }  // namespace tfsc

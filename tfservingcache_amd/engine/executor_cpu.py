@@ -183,9 +183,17 @@ class CpuExecutor:
             v = _get(op.inputs[2])
             scale = p["scale"]
             scores = np.einsum("bqhd,bkhd->bhqk", q, kk_) * scale
+            if len(op.inputs) > 3:
+                bias = _get(op.inputs[3])
+                bias = bias.reshape((1,) * (4 - bias.ndim) + bias.shape)
+                scores = scores + np.broadcast_to(bias, scores.shape)
             mx = scores.max(-1, keepdims=True)
+            # -inf biases: a fully masked row has max -inf; keep the
+            # subtraction finite and let the row come out as zeros
+            mx = np.where(np.isfinite(mx), mx, 0.0)
             e = np.exp(scores - mx)
-            probs = e / e.sum(-1, keepdims=True)
+            den = e.sum(-1, keepdims=True)
+            probs = e / np.where(den > 0, den, 1.0)
             ctx = np.einsum("bhqk,bkhd->bqhd", probs, v)
             vals[op.outputs[0]] = ctx.astype(np.float32)
         elif k == "concat":

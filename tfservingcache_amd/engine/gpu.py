@@ -675,12 +675,29 @@ class ExecContext:
                 calls.extend(self._c_bgemm(op, ext))
             elif k == "attention":
                 b_, s_, h_, d_ = self.shapes[op.inputs[0]]
-                calls.append((ext.K_ATTENTION,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.inputs[1]),
-                               self._ptr(op.inputs[2]),
-                               self._ptr(op.outputs[0])],
-                              [b_, s_, h_, d_],
+                ptrs = [self._ptr(op.inputs[0]),
+                        self._ptr(op.inputs[1]),
+                        self._ptr(op.inputs[2]),
+                        self._ptr(op.outputs[0])]
+                ints = [b_, s_, h_, d_]
+                if len(op.inputs) > 3:
+                    # additive bias [b,h,q,S] (rank-4 padded), element
+                    # strides with 0 = broadcast; checked against the
+                    # resolved shape so a stride never walks past it
+                    bshape = tuple(self.shapes[op.inputs[3]])
+                    bshape = (1,) * (4 - len(bshape)) + bshape
+                    batched, bh, bq = p["bias_dims"]
+                    want = (b_ if batched else 1, bh, bq, s_)
+                    if bshape != want or bh not in (1, h_) or \
+                            bq not in (1, s_):
+                        raise ValueError(
+                            f"attention bias shape {bshape} does not "
+                            f"match plan {want}")
+                    ptrs.append(self._ptr(op.inputs[3]))
+                    ints += [bh * bq * s_ if batched else 0,
+                             bq * s_ if bh == h_ else 0,
+                             s_ if bq == s_ else 0]
+                calls.append((ext.K_ATTENTION, ptrs, ints,
                               [float(p["scale"])]))
             elif k == "softmax":
                 shape = self.shapes[op.inputs[0]]

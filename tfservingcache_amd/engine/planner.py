@@ -1324,17 +1324,47 @@ def _broadcast(sa: Sequence[Dim], sb: Sequence[Dim]) -> Shape:
     return tuple(reversed(out))
 
 
+def _attention_bias_dims(bias_t: PlanTensor, qshape: Shape):
+    """(b_is_batch, h, q) when bias_t can ride the fused attention
+    kernel as an additive score bias, else None. Eligible: f32
+    activation/input/weight whose shape, left-padded with 1s to rank 4,
+    is [b, h, q, S] with b in {B (coefficient 1), 1}, h in {1, H},
+    q in {1, S}."""
+    if bias_t.dtype != "f32" or \
+            bias_t.kind not in ("activation", "input", "weight"):
+        return None
+    bs = tuple(bias_t.shape)
+    if len(bs) > 4 or len(bs) == 0:
+        return None
+    bs = (1,) * (4 - len(bs)) + bs
+    seq, heads = qshape[1], qshape[2]
+    if is_sym(seq) or is_sym(heads) or any(is_sym(d) for d in bs[1:]):
+        return None
+    if bs[0] not in (B, 1) or bs[1] not in (1, heads) or \
+            bs[2] not in (1, seq) or bs[3] != seq:
+        return None
+    if bs[0] == B and qshape[0] != B:
+        return None
+    return (bs[0] == B, int(bs[1]), int(bs[2]))
+
+
 def fuse_attention(plan: Plan) -> Plan:
     """Post-pass: collapse the lowered multi-head-attention op chain
 
         transpose(q4d) , transpose(k4d) , transpose(v4d)   [perm 0,2,1,3]
-        batched_gemm(qh, kh, trans_b=True) -> eltwise mul(scalar)
+        batched_gemm(qh, kh, trans_b=True)
+        -> eltwise mul(scalar) | eltwise div(scores, scalar)
+        [-> eltwise add(bias), either operand order]
         -> softmax -> batched_gemm(probs, vh) -> transpose [perm 0,2,1,3]
 
     into one `attention` op operating on the PRE-transpose [B,S,H,D]
     views (flash-style fused kernel on GPU; no S x S materialization,
-    no transposes). Fused only when head_dim == 64 (the kernel's
-    constraint); otherwise left as-is."""
+    no transposes). The optional add is the attention mask of real
+    exports ((1 - mask) * -10000 as [B,1,1,S], or a constant [1,1,S,S]
+    causal bias); it becomes a 4th input plus `bias_dims` (see
+    _attention_bias_dims) and may be shared by every layer. Fused only
+    when head_dim == 64 (the kernel's constraint) and the bias is
+    eligible; otherwise left as-is."""
     ops = plan.ops
     produced_by: Dict[int, int] = {}
     for oi, op in enumerate(ops):
@@ -1368,16 +1398,47 @@ def fuse_attention(plan: Plan) -> Plan:
             continue
         mul_oi = sole_consumer(op.outputs[0])
         if mul_oi is None or ops[mul_oi].kind != "eltwise" or \
-                ops[mul_oi].params.get("fn") != "mul":
+                len(ops[mul_oi].inputs) != 2 or \
+                ops[mul_oi].params.get("fn") not in ("mul", "div"):
             continue
         mul_op = ops[mul_oi]
-        scale_idx = mul_op.inputs[1] if mul_op.inputs[0] == op.outputs[0] \
-            else mul_op.inputs[0]
+        scores_first = mul_op.inputs[0] == op.outputs[0]
+        if mul_op.params["fn"] == "div" and (
+                not scores_first or
+                mul_op.inputs[1] == op.outputs[0]):
+            continue                    # c / scores is not a scaling
+        scale_idx = mul_op.inputs[1] if scores_first else mul_op.inputs[0]
         scale_t = plan.tensors[scale_idx]
         if scale_t.weight is None or scale_t.weight.size != 1:
             continue
         scale = float(np.asarray(scale_t.weight).reshape(-1)[0])
+        if mul_op.params["fn"] == "div":
+            if scale == 0.0:
+                continue
+            scale = 1.0 / scale
+        q4d, k4d = tq.inputs[0], tk.inputs[0]
+        shape = plan.tensors[q4d].shape        # [B, S, H, D]
+        if len(shape) != 4 or shape[3] != 64:
+            continue
+        # optional additive bias (attention mask) on the scaled scores
         sm_oi = sole_consumer(mul_op.outputs[0])
+        add_oi = None
+        bias_idx = None
+        bias_dims = None
+        if sm_oi is not None and ops[sm_oi].kind == "eltwise" and \
+                ops[sm_oi].params.get("fn") == "add" and \
+                len(ops[sm_oi].inputs) == 2:
+            add_op = ops[sm_oi]
+            if add_op.inputs[0] == add_op.inputs[1]:
+                continue
+            bias_idx = add_op.inputs[1] \
+                if add_op.inputs[0] == mul_op.outputs[0] \
+                else add_op.inputs[0]
+            bias_dims = _attention_bias_dims(plan.tensors[bias_idx], shape)
+            if bias_dims is None:
+                continue
+            add_oi = sm_oi
+            sm_oi = sole_consumer(add_op.outputs[0])
         if sm_oi is None or ops[sm_oi].kind != "softmax":
             continue
         pv_oi = sole_consumer(ops[sm_oi].outputs[0])
@@ -1394,18 +1455,20 @@ def fuse_attention(plan: Plan) -> Plan:
                 ops[tc_oi].params.get("perm") != [0, 2, 1, 3]:
             continue
         tc = ops[tc_oi]
-        q4d, k4d, v4d = tq.inputs[0], tk.inputs[0], tv.inputs[0]
-        shape = plan.tensors[q4d].shape        # [B, S, H, D]
-        if len(shape) != 4 or shape[3] != 64:
-            continue
+        v4d = tv.inputs[0]
         for rm in (produced_by[tq.outputs[0]], produced_by[tk.outputs[0]],
                    produced_by[tv.outputs[0]], oi, mul_oi, sm_oi, pv_oi,
                    tc_oi):
             to_remove.add(rm)
-        replacements[tc_oi] = PlanOp(
-            "attention", [q4d, k4d, v4d], [tc.outputs[0]],
-            {"scale": scale, "seq": shape[1], "heads": shape[2],
-             "head_dim": shape[3]})
+        inputs = [q4d, k4d, v4d]
+        params = {"scale": scale, "seq": shape[1], "heads": shape[2],
+                  "head_dim": shape[3]}
+        if add_oi is not None:
+            to_remove.add(add_oi)
+            inputs.append(bias_idx)
+            params["bias_dims"] = bias_dims
+        replacements[tc_oi] = PlanOp("attention", inputs,
+                                     [tc.outputs[0]], params)
 
     if not to_remove:
         return plan

@@ -277,7 +277,12 @@ def build_mobilenet_v2(image_size=224, num_classes=1000, seed=0,
 # pooler. Frozen-graph decompositions for LayerNorm and GELU.
 # ---------------------------------------------------------------------------
 def build_bert(seq_len=128, hidden=768, layers=12, heads=12,
-               intermediate=3072, vocab=30522, seed=0):
+               intermediate=3072, vocab=30522, seed=0, with_mask=False):
+    """with_mask=True adds the `input_mask` placeholder (int32 [B, S],
+    1 = token, 0 = padding) of real BERT exports and its additive
+    attention bias (1 - mask) * -10000, shaped [B,1,1,S] and added to
+    the scaled scores of every layer. Weights for a given seed are the
+    same either way."""
     rng = np.random.default_rng(seed)
     gb = GraphBuilder()
     f32 = gb.a_type(1)
@@ -350,6 +355,21 @@ def build_bert(seq_len=128, hidden=768, layers=12, heads=12,
     perm = gb.const("perm0213", np.array([0, 2, 1, 3], dtype=np.int32))
     to_ctx = gb.const("to_ctx", np.array([-1, hidden], dtype=np.int32))
 
+    mask_bias = None
+    if with_mask:
+        mask = gb.placeholder("input_mask", np.int32, [-1, seq_len],
+                              signature_name="input_mask")
+        mask_f = gb.node("Cast", "mask/cast", [mask], SrcT=i32, DstT=f32)
+        inv = gb.node("Sub", "mask/inv",
+                      [gb.const("mask/one", np.float32(1.0)), mask_f], T=f32)
+        neg = gb.node("Mul", "mask/neg",
+                      [inv, gb.const("mask/neg_c", np.float32(-10000.0))],
+                      T=f32)
+        mask_bias = gb.node(
+            "Reshape", "mask/bias",
+            [neg, gb.const("mask/shape",
+                           np.array([-1, 1, 1, seq_len], dtype=np.int32))])
+
     for li in range(layers):
         pre = f"layer{li}"
         q = dense(f"{pre}/q", h, hidden, hidden)
@@ -367,6 +387,9 @@ def build_bert(seq_len=128, hidden=768, layers=12, heads=12,
         scores = gb.node("BatchMatMulV2", f"{pre}/scores", [qh, kh],
                          T=f32, adj_x=gb.a_bool(False), adj_y=gb.a_bool(True))
         scaled = gb.node("Mul", f"{pre}/scaled", [scores, scale], T=f32)
+        if mask_bias is not None:
+            scaled = gb.node("AddV2", f"{pre}/masked", [scaled, mask_bias],
+                             T=f32)
         probs = gb.node("Softmax", f"{pre}/probs", [scaled], T=f32)
         ctx = gb.node("BatchMatMulV2", f"{pre}/ctx", [probs, vh], T=f32)
         ctx_t = gb.node("Transpose", f"{pre}/ctx_t", [ctx, perm], T=f32)
