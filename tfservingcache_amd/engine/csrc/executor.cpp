@@ -46,6 +46,8 @@ enum CallKind : int {
   K_CAST,
   K_ARGMAX_LAST,
   K_SCATTER,
+  K_RESIZE,
+  K_ZERO_INSERT,
 };
 
 struct Call {
@@ -199,6 +201,31 @@ static void launch_call(const Call& c, hipStream_t s) {
                             int(I[9]), int(I[10]), int(I[11]),
                             int(I[12]));
       break;
+    case K_RESIZE: {
+      // ptrs: [x, y]
+      // ints: [N,H,W,C,Ho,Wo,mode(0 nearest|1 bilinear),align_corners,
+      //        half_pixel_centers]
+      if (c.ptrs.size() != 2 || I.size() != 9)
+        throw std::runtime_error("resize needs 2 ptrs and 9 ints");
+      for (int k = 0; k < 7; ++k)
+        if (I[k] < 0 || I[k] > INT32_MAX)
+          throw std::runtime_error("resize: int out of range");
+      launch_resize_nhwc(s, cp(0), p(1), int(I[0]), int(I[1]), int(I[2]),
+                         int(I[3]), int(I[4]), int(I[5]), int(I[6]),
+                         I[7] != 0, I[8] != 0);
+      break;
+    }
+    case K_ZERO_INSERT: {
+      // ptrs: [x, y]; ints: [N,h,w,C,sh,sw]
+      if (c.ptrs.size() != 2 || I.size() != 6)
+        throw std::runtime_error("zero_insert needs 2 ptrs and 6 ints");
+      for (int k = 0; k < 6; ++k)
+        if (I[k] < 0 || I[k] > INT32_MAX)
+          throw std::runtime_error("zero_insert: int out of range");
+      launch_zero_insert_nhwc(s, cp(0), p(1), int(I[0]), int(I[1]),
+                              int(I[2]), int(I[3]), int(I[4]), int(I[5]));
+      break;
+    }
     default:
       throw std::runtime_error("unknown call kind " +
                                std::to_string(c.kind));
@@ -378,6 +405,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("K_CAST") = int(tfsc::K_CAST);
   mod.attr("K_ARGMAX_LAST") = int(tfsc::K_ARGMAX_LAST);
   mod.attr("K_SCATTER") = int(tfsc::K_SCATTER);
+  mod.attr("K_RESIZE") = int(tfsc::K_RESIZE);
+  mod.attr("K_ZERO_INSERT") = int(tfsc::K_ZERO_INSERT);
 
   py::class_<tfsc::CallTemplate>(mod, "CallTemplate")
       .def(py::init([](py::list calls) {

@@ -129,6 +129,22 @@ void launch_depthwise_conv(hipStream_t s, const ushort* x, const ushort* w,
                            int sh, int sw, int pt, int pl, int Ho, int Wo,
                            int act);
 
+// NHWC image resize with TF's coordinate rules (ResizeNearestNeighbor /
+// ResizeBilinear): mode 0 = nearest, 1 = bilinear. The per-axis scale is
+// (in-1)/(out-1) when align_corners and out > 1, else in/out, computed
+// here in f32 and passed to the kernel. Bilinear lerps in f32 and rounds
+// to bf16 once. 16-byte vector path when C % 8 == 0. Throws on
+// non-positive dims, an unknown mode, or both flags set.
+void launch_resize_nhwc(hipStream_t s, const ushort* x, ushort* y, int N,
+                        int H, int W, int C, int Ho, int Wo, int mode,
+                        bool align_corners, bool half_pixel_centers);
+
+// Zero-insertion (transposed-conv input dilation):
+//   y[n, i*sh, j*sw, c] = x[n,i,j,c], every other element 0, with
+//   y [N, (h-1)*sh+1, (w-1)*sw+1, C]. Writes all of y in one pass.
+void launch_zero_insert_nhwc(hipStream_t s, const ushort* x, ushort* y,
+                             int N, int h, int w, int C, int sh, int sw);
+
 // fp8 (OCP e4m3) GEMM with rowwise dequant in the f32 epilogue:
 // C[M,N] = act(acc(Aq @ Bq^T) * sa[m] * sb[n] + bias [+ residual]).
 // Aq/Bq are e4m3 bytes with K padded to a multiple of 128; B^T layout

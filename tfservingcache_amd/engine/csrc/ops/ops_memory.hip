@@ -879,4 +879,230 @@ void launch_argmax_last(hipStream_t s, const ushort* x, int* y,
                      rows, cols);
 }
 
+// ---------------------------------------------------------------------------
+// image resize (NHWC; TF ResizeNearestNeighbor / ResizeBilinear) and
+// zero-insertion (the input dilation of a transposed conv). Same design
+// as pooling: one thread per 8 channels of one output pixel with 16-byte
+// loads/stores when C % 8 == 0, one thread per element otherwise.
+// Source coordinates are f32 and use the unfused *_rn forms so they
+// round exactly like the CPU executor's (no fma contraction); every
+// source index is clamped into the image.
+// ---------------------------------------------------------------------------
+struct ResizeGeom {
+  int N, H, W, C, Ho, Wo;
+  int align, half;        // align_corners / half_pixel_centers (0|1)
+  float hscale, wscale;   // computed on the host in f32
+};
+
+TFSC_DEV int resize_nearest_idx(int d, float scale, int n_in, int align,
+                                int half) {
+  float src = half ? __fmul_rn(float(d) + 0.5f, scale)
+                   : __fmul_rn(float(d), scale);
+  int i = int(align ? roundf(src) : floorf(src));
+  return min(max(i, 0), n_in - 1);
+}
+
+TFSC_DEV void resize_bilinear_coord(int d, float scale, int n_in, int half,
+                                    int& lo, int& hi, float& lerp) {
+  float src = half ? __fsub_rn(__fmul_rn(float(d) + 0.5f, scale), 0.5f)
+                   : __fmul_rn(float(d), scale);
+  float fl = floorf(src);
+  lo = min(max(int(fl), 0), n_in - 1);
+  hi = min(max(int(ceilf(src)), 0), n_in - 1);
+  lerp = src - fl;
+}
+
+TFSC_DEV float resize_lerp2(float tl, float tr, float bl, float br,
+                            float lx, float ly) {
+  float top = tl + (tr - tl) * lx;
+  float bot = bl + (br - bl) * lx;
+  return top + (bot - top) * ly;
+}
+
+// low / high bf16 of a packed 32-bit word as f32
+TFSC_DEV float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
+TFSC_DEV float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+
+TFSC_DEV uint32_t resize_lerp_pair(uint32_t tl, uint32_t tr, uint32_t bl,
+                                   uint32_t br, float lx, float ly) {
+  return f2bf2(
+      resize_lerp2(bf_lo(tl), bf_lo(tr), bf_lo(bl), bf_lo(br), lx, ly),
+      resize_lerp2(bf_hi(tl), bf_hi(tr), bf_hi(bl), bf_hi(br), lx, ly));
+}
+
+template <bool BILINEAR>
+__global__ void k_resize_v8(const ushort* __restrict__ x,
+                            ushort* __restrict__ y, ResizeGeom g) {
+  int c8 = g.C >> 3;
+  int64_t n_grp = (int64_t)g.N * g.Ho * g.Wo * c8;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_grp; i += stride) {
+    int grp = int(i % c8);
+    int64_t t = i / c8;
+    int wo = int(t % g.Wo); t /= g.Wo;
+    int ho = int(t % g.Ho); int n = int(t / g.Ho);
+    const ushort* img = x + (int64_t)n * g.H * g.W * g.C + grp * 8;
+    auto px = [&](int hi, int wi) {
+      return *reinterpret_cast<const uint4*>(
+          img + ((int64_t)hi * g.W + wi) * g.C);
+    };
+    uint4 out;
+    if (BILINEAR) {
+      int y0, y1, x0, x1;
+      float ly, lx;
+      resize_bilinear_coord(ho, g.hscale, g.H, g.half, y0, y1, ly);
+      resize_bilinear_coord(wo, g.wscale, g.W, g.half, x0, x1, lx);
+      uint4 tl = px(y0, x0), tr = px(y0, x1);
+      uint4 bl = px(y1, x0), br = px(y1, x1);
+      out.x = resize_lerp_pair(tl.x, tr.x, bl.x, br.x, lx, ly);
+      out.y = resize_lerp_pair(tl.y, tr.y, bl.y, br.y, lx, ly);
+      out.z = resize_lerp_pair(tl.z, tr.z, bl.z, br.z, lx, ly);
+      out.w = resize_lerp_pair(tl.w, tr.w, bl.w, br.w, lx, ly);
+    } else {
+      out = px(resize_nearest_idx(ho, g.hscale, g.H, g.align, g.half),
+               resize_nearest_idx(wo, g.wscale, g.W, g.align, g.half));
+    }
+    *reinterpret_cast<uint4*>(y + i * 8) = out;
+  }
+}
+
+template <bool BILINEAR>
+__global__ void k_resize(const ushort* __restrict__ x,
+                         ushort* __restrict__ y, ResizeGeom g) {
+  int64_t n_out = (int64_t)g.N * g.Ho * g.Wo * g.C;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_out; i += stride) {
+    int c = int(i % g.C);
+    int64_t t = i / g.C;
+    int wo = int(t % g.Wo); t /= g.Wo;
+    int ho = int(t % g.Ho); int n = int(t / g.Ho);
+    const ushort* img = x + (int64_t)n * g.H * g.W * g.C + c;
+    auto px = [&](int hi, int wi) {
+      return img[((int64_t)hi * g.W + wi) * g.C];
+    };
+    if (BILINEAR) {
+      int y0, y1, x0, x1;
+      float ly, lx;
+      resize_bilinear_coord(ho, g.hscale, g.H, g.half, y0, y1, ly);
+      resize_bilinear_coord(wo, g.wscale, g.W, g.half, x0, x1, lx);
+      y[i] = f2bf(resize_lerp2(bf2f(px(y0, x0)), bf2f(px(y0, x1)),
+                               bf2f(px(y1, x0)), bf2f(px(y1, x1)),
+                               lx, ly));
+    } else {
+      y[i] = px(resize_nearest_idx(ho, g.hscale, g.H, g.align, g.half),
+                resize_nearest_idx(wo, g.wscale, g.W, g.align, g.half));
+    }
+  }
+}
+
+static inline bool aligned16(const void* a, const void* b) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) &
+          15u) == 0;
+}
+
+static inline float resize_scale(int n_in, int n_out, bool align_corners) {
+  return (align_corners && n_out > 1)
+             ? float(n_in - 1) / float(n_out - 1)
+             : float(n_in) / float(n_out);
+}
+
+void launch_resize_nhwc(hipStream_t s, const ushort* x, ushort* y, int N,
+                        int H, int W, int C, int Ho, int Wo, int mode,
+                        bool align_corners, bool half_pixel_centers) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0)
+    throw std::runtime_error("resize: every dimension must be positive");
+  if (mode != 0 && mode != 1)
+    throw std::runtime_error("resize: mode must be 0 (nearest) or 1 "
+                             "(bilinear), got " + std::to_string(mode));
+  if (align_corners && half_pixel_centers)
+    throw std::runtime_error("resize: align_corners and "
+                             "half_pixel_centers are mutually exclusive");
+  ResizeGeom g{N, H, W, C, Ho, Wo, align_corners ? 1 : 0,
+               half_pixel_centers ? 1 : 0,
+               resize_scale(H, Ho, align_corners),
+               resize_scale(W, Wo, align_corners)};
+  if (C % 8 == 0 && aligned16(x, y)) {
+    int64_t n_grp = (int64_t)N * Ho * Wo * (C / 8);
+    if (mode == 1)
+      hipLaunchKernelGGL(k_resize_v8<true>, dim3(grid_for(n_grp)),
+                         dim3(TPB), 0, s, x, y, g);
+    else
+      hipLaunchKernelGGL(k_resize_v8<false>, dim3(grid_for(n_grp)),
+                         dim3(TPB), 0, s, x, y, g);
+    return;
+  }
+  int64_t n_out = (int64_t)N * Ho * Wo * C;
+  if (mode == 1)
+    hipLaunchKernelGGL(k_resize<true>, dim3(grid_for(n_out)), dim3(TPB), 0,
+                       s, x, y, g);
+  else
+    hipLaunchKernelGGL(k_resize<false>, dim3(grid_for(n_out)), dim3(TPB), 0,
+                       s, x, y, g);
+}
+
+// zero-insert: x [N,h,w,C] -> y [N,(h-1)*sh+1,(w-1)*sw+1,C] with x at the
+// (sh, sw)-strided positions. EVERY output element is written (data or
+// zero) in the one pass: y lives in the liveness-reused workspace arena,
+// so it holds another tensor's bytes when the kernel starts.
+__global__ void k_zero_insert_v8(const ushort* __restrict__ x,
+                                 ushort* __restrict__ y, int N, int h,
+                                 int w, int C, int sh, int sw, int Ho,
+                                 int Wo) {
+  int c8 = C >> 3;
+  int64_t n_grp = (int64_t)N * Ho * Wo * c8;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_grp; i += stride) {
+    int grp = int(i % c8);
+    int64_t t = i / c8;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    uint4 v = uint4{0, 0, 0, 0};
+    if (ho % sh == 0 && wo % sw == 0)
+      v = *reinterpret_cast<const uint4*>(
+          x + (((int64_t)n * h + ho / sh) * w + wo / sw) * C + grp * 8);
+    *reinterpret_cast<uint4*>(y + i * 8) = v;
+  }
+}
+
+__global__ void k_zero_insert(const ushort* __restrict__ x,
+                              ushort* __restrict__ y, int N, int h, int w,
+                              int C, int sh, int sw, int Ho, int Wo) {
+  int64_t n_out = (int64_t)N * Ho * Wo * C;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_out; i += stride) {
+    int c = int(i % C);
+    int64_t t = i / C;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    ushort v = 0;
+    if (ho % sh == 0 && wo % sw == 0)
+      v = x[(((int64_t)n * h + ho / sh) * w + wo / sw) * C + c];
+    y[i] = v;
+  }
+}
+
+void launch_zero_insert_nhwc(hipStream_t s, const ushort* x, ushort* y,
+                             int N, int h, int w, int C, int sh, int sw) {
+  if (N <= 0 || h <= 0 || w <= 0 || C <= 0 || sh <= 0 || sw <= 0)
+    throw std::runtime_error(
+        "zero_insert: every dimension and stride must be positive");
+  int64_t Ho64 = (int64_t)(h - 1) * sh + 1, Wo64 = (int64_t)(w - 1) * sw + 1;
+  if (Ho64 > INT32_MAX || Wo64 > INT32_MAX)
+    throw std::runtime_error("zero_insert: output image too large");
+  int Ho = int(Ho64), Wo = int(Wo64);
+  if (C % 8 == 0 && aligned16(x, y)) {
+    int64_t n_grp = (int64_t)N * Ho * Wo * (C / 8);
+    hipLaunchKernelGGL(k_zero_insert_v8, dim3(grid_for(n_grp)), dim3(TPB),
+                       0, s, x, y, N, h, w, C, sh, sw, Ho, Wo);
+    return;
+  }
+  int64_t n_out = (int64_t)N * Ho * Wo * C;
+  hipLaunchKernelGGL(k_zero_insert, dim3(grid_for(n_out)), dim3(TPB), 0, s,
+                     x, y, N, h, w, C, sh, sw, Ho, Wo);
+}
+
 }  // namespace tfsc

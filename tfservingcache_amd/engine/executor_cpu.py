@@ -53,6 +53,58 @@ _BINARY = {
 }
 
 
+def _resize_scale(n_in: int, n_out: int, align_corners: bool) -> np.float32:
+    if align_corners and n_out > 1:
+        return np.float32(n_in - 1) / np.float32(n_out - 1)
+    return np.float32(n_in) / np.float32(n_out)
+
+
+def _resize_nearest_idx(n_in, n_out, align_corners, half_pixel):
+    """Source index per output index along one axis (TF
+    ResizeNearestNeighbor), coordinates in f32."""
+    d = np.arange(n_out, dtype=np.float32)
+    scale = _resize_scale(n_in, n_out, align_corners)
+    src = (d + np.float32(0.5)) * scale if half_pixel else d * scale
+    fl = np.floor(src)
+    if align_corners:
+        # roundf: halves away from zero (src >= 0; src - fl is exact)
+        fl = fl + (src - fl >= np.float32(0.5))
+    return np.clip(fl.astype(np.int64), 0, n_in - 1)
+
+
+def _resize_bilinear_coords(n_in, n_out, align_corners, half_pixel):
+    """(lo, hi, lerp) per output index along one axis (TF
+    ResizeBilinear), coordinates in f32."""
+    d = np.arange(n_out, dtype=np.float32)
+    scale = _resize_scale(n_in, n_out, align_corners)
+    if half_pixel:
+        src = (d + np.float32(0.5)) * scale - np.float32(0.5)
+    else:
+        src = d * scale
+    fl = np.floor(src)
+    lo = np.clip(fl.astype(np.int64), 0, n_in - 1)
+    hi = np.clip(np.ceil(src).astype(np.int64), 0, n_in - 1)
+    return lo, hi, (src - fl).astype(np.float32)
+
+
+def _resize(x, out_hw, mode, align_corners, half_pixel):
+    """NHWC image resize, f32. Bilinear interpolates along x, then y."""
+    _, H, W, _ = x.shape
+    Ho, Wo = out_hw
+    if mode == "nearest":
+        iy = _resize_nearest_idx(H, Ho, align_corners, half_pixel)
+        ix = _resize_nearest_idx(W, Wo, align_corners, half_pixel)
+        return np.ascontiguousarray(x[:, iy][:, :, ix], dtype=np.float32)
+    y0, y1, ly = _resize_bilinear_coords(H, Ho, align_corners, half_pixel)
+    x0, x1, lx = _resize_bilinear_coords(W, Wo, align_corners, half_pixel)
+    lx = lx[None, None, :, None]
+    ly = ly[None, :, None, None]
+    rows0, rows1 = x[:, y0], x[:, y1]
+    top = rows0[:, :, x0] + (rows0[:, :, x1] - rows0[:, :, x0]) * lx
+    bot = rows1[:, :, x0] + (rows1[:, :, x1] - rows1[:, :, x0]) * lx
+    return (top + (bot - top) * ly).astype(np.float32)
+
+
 class CpuExecutor:
     def __init__(self, plan: Plan):
         self.plan = plan
@@ -223,6 +275,17 @@ class CpuExecutor:
         elif k == "argmax_last":
             x = _get(op.inputs[0])
             vals[op.outputs[0]] = x.argmax(axis=-1).astype(np.int32)
+        elif k == "resize":
+            vals[op.outputs[0]] = _resize(
+                _get(op.inputs[0]), p["out_hw"], p["mode"],
+                p["align_corners"], p["half_pixel_centers"])
+        elif k == "zero_insert":
+            x = _get(op.inputs[0])          # [N,h,w,C]
+            sh, sw = p["stride"]
+            Hz, Wz = p["out_hw"]
+            z = np.zeros((x.shape[0], Hz, Wz, x.shape[3]), dtype=np.float32)
+            z[:, ::sh, ::sw, :] = x
+            vals[op.outputs[0]] = z
         else:
             raise ValueError(f"unknown plan op {k}")
 

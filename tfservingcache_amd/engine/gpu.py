@@ -757,6 +757,30 @@ class ExecContext:
                               [1 if p["mode"] == "max" else 0,
                                n, h, w, c, ho, wo, kh, kw, sh, sw, pt, pl],
                               []))
+            elif k == "resize":
+                n, h, w, c = self.shapes[op.inputs[0]]
+                ho, wo = p["out_hw"]
+                if (h, w) != tuple(p["in_hw"]) or \
+                        p["mode"] not in ("nearest", "bilinear"):
+                    raise RuntimeError(f"GPU resize: bad params {p}")
+                calls.append((ext.K_RESIZE,
+                              [self._ptr(op.inputs[0]),
+                               self._ptr(op.outputs[0])],
+                              [n, h, w, c, ho, wo,
+                               1 if p["mode"] == "bilinear" else 0,
+                               1 if p["align_corners"] else 0,
+                               1 if p["half_pixel_centers"] else 0],
+                              []))
+            elif k == "zero_insert":
+                n, h, w, c = self.shapes[op.inputs[0]]
+                sh, sw = p["stride"]
+                if tuple(self.shapes[op.outputs[0]]) != \
+                        (n, (h - 1) * sh + 1, (w - 1) * sw + 1, c):
+                    raise RuntimeError(f"GPU zero_insert: bad params {p}")
+                calls.append((ext.K_ZERO_INSERT,
+                              [self._ptr(op.inputs[0]),
+                               self._ptr(op.outputs[0])],
+                              [n, h, w, c, sh, sw], []))
             elif k == "transpose":
                 in_shape = self.shapes[op.inputs[0]]
                 perm = p["perm"]

@@ -147,10 +147,17 @@ _ELTWISE_UNARY = {"Relu": "relu", "Relu6": "relu6", "Tanh": "tanh",
 _ELTWISE_BINARY = {"Add": "add", "AddV2": "add", "Sub": "sub", "Mul": "mul",
                    "RealDiv": "div", "Maximum": "max", "Minimum": "min",
                    "SquaredDifference": "sqdiff"}
+# shape arithmetic Keras exports build around Shape(x); folded to a
+# constant when every operand is an integer constant (try_fold_int)
+_INT_FOLDABLE = ("StridedSlice", "Pack", "Mul", "Add", "AddV2", "Sub")
 
 
 class _Lowerer:
     """One-pass topological lowering with peephole fusion."""
+
+    # measurement switch (scripts/upsampling_probe.py): False sends
+    # kernel == stride transposed convs down the general lowering too
+    DECONV_GEMM_LOWERING = True
 
     def __init__(self, graph_def: g.GraphDef,
                  signature: m.SignatureDef,
@@ -350,8 +357,16 @@ class _Lowerer:
             if cv is not None:
                 self.consts[nd.name] = cv
             return
+        if op in _INT_FOLDABLE and self.try_fold_int(nd, out):
+            return
         if op == "Reshape":
             self.lower_reshape(nd, out)
+            return
+        if op in ("ResizeNearestNeighbor", "ResizeBilinear"):
+            self.lower_resize(nd, out)
+            return
+        if op == "Conv2DBackpropInput":
+            self.lower_conv_transpose(nd, out)
             return
         if op in ("Squeeze", "ExpandDims"):
             self.lower_squeeze_expand(nd, out)
@@ -716,6 +731,250 @@ class _Lowerer:
                                      "activation", out_name)
                 self.ops.append(PlanOp("eltwise", [y], [y3], {"fn": act}))
                 y = y3
+        if out_name != out:
+            self.by_name[out] = y
+
+    def try_fold_int(self, nd: g.NodeDef, out: str) -> bool:
+        """Fold StridedSlice / Pack / Mul / Add / Sub over integer
+        constants already in self.consts (the arithmetic Keras wraps
+        around Shape(x) to build Conv2DTranspose's input_sizes and
+        UpSampling2D's size). Registers the result like the Shape case.
+        Returns False — leaving the node to its ordinary lowering —
+        when any operand is not such a constant."""
+        vals = []
+        for ref in nd.input:
+            if ref.startswith("^"):
+                continue
+            if _tensor_name(ref) != _node_of(ref) + ":0":
+                return False
+            v = self.consts.get(_node_of(ref))
+            if v is None:
+                return False
+            v = np.asarray(v)
+            if v.dtype not in (np.int32, np.int64):
+                return False
+            vals.append(v)
+        op = nd.op
+        if op == "StridedSlice":
+            if len(vals) != 4 or _attr_i(nd, "ellipsis_mask", 0) or \
+                    _attr_i(nd, "new_axis_mask", 0):
+                return False
+            x, begin, end, strides = vals
+            if not (begin.ndim == end.ndim == strides.ndim == 1) or \
+                    not (len(begin) == len(end) == len(strides)) or \
+                    len(begin) > x.ndim or any(int(s) <= 0 for s in strides):
+                return False
+            bm = _attr_i(nd, "begin_mask", 0)
+            em = _attr_i(nd, "end_mask", 0)
+            sm = _attr_i(nd, "shrink_axis_mask", 0)
+            sl = []
+            for d in range(len(begin)):
+                b, e = int(begin[d]), int(end[d])
+                if (sm >> d) & 1:
+                    if not -x.shape[d] <= b < x.shape[d]:
+                        return False
+                    sl.append(b)
+                else:
+                    sl.append(slice(None if (bm >> d) & 1 else b,
+                                    None if (em >> d) & 1 else e,
+                                    int(strides[d])))
+            res = x[tuple(sl)]
+        elif op == "Pack":
+            if not vals:
+                return False
+            if any(v.shape != vals[0].shape for v in vals):
+                # a scalar Const may decode as shape (1,) (an empty
+                # TensorShapeProto is not kept on the wire)
+                if any(v.size != 1 for v in vals):
+                    return False
+                vals = [v.reshape(()) for v in vals]
+            axis = _attr_i(nd, "axis", 0)
+            if not -(vals[0].ndim + 1) <= axis <= vals[0].ndim:
+                return False
+            res = np.stack(vals, axis=axis)
+        else:
+            if len(vals) != 2:
+                return False
+            fn = {"Mul": np.multiply, "Sub": np.subtract}.get(op, np.add)
+            try:
+                res = fn(vals[0], vals[1])
+            except ValueError:
+                return False
+        res = np.array(res, dtype=vals[0].dtype)     # 0-d stays 0-d
+        self.consts[nd.name] = res
+        self.new_tensor(tuple(res.shape), "i32", "weight", out, weight=res)
+        return True
+
+    def lower_resize(self, nd: g.NodeDef, out: str) -> None:
+        """ResizeNearestNeighbor / ResizeBilinear with a constant size
+        -> `resize` (NHWC f32). Coordinates follow TF's kernels, in f32
+        (executor_cpu.py `_resize` is the exact definition)."""
+        x = self.tid(nd.input[0])
+        xt = self.tensors[x]
+        if len(xt.shape) != 4:
+            raise PlanError(f"{nd.op} needs a rank-4 NHWC input "
+                            f"(got rank {len(xt.shape)})")
+        if xt.dtype != "f32":
+            raise PlanError(f"{nd.op} on non-f32 input unsupported")
+        size = self.const_value(nd.input[1])
+        if size is None:
+            raise PlanError(f"dynamic {nd.op} size unsupported")
+        size = np.asarray(size).reshape(-1)
+        if size.size != 2 or size.dtype not in (np.int32, np.int64):
+            raise PlanError(f"{nd.op} size must be two integers")
+        align = _attr_b(nd, "align_corners", False)
+        half = _attr_b(nd, "half_pixel_centers", False)
+        if align and half:
+            raise PlanError(f"{nd.op}: align_corners and "
+                            "half_pixel_centers are mutually exclusive")
+        if is_sym(xt.shape[1]) or is_sym(xt.shape[2]) or \
+                is_sym(xt.shape[3]):
+            raise PlanError(f"{nd.op} needs concrete H, W, C")
+        H, W, C = int(xt.shape[1]), int(xt.shape[2]), int(xt.shape[3])
+        Ho, Wo = int(size[0]), int(size[1])
+        if min(H, W, C, Ho, Wo) <= 0:
+            raise PlanError(f"{nd.op}: empty image ({H}x{W} -> {Ho}x{Wo})")
+        if (Ho, Wo) == (H, W):
+            # every source coordinate is the pixel itself in all modes
+            self.new_tensor(xt.shape, xt.dtype, xt.kind, out, alias_of=x)
+            return
+        y = self.new_tensor((xt.shape[0], Ho, Wo, C), "f32", "activation",
+                            out)
+        self.ops.append(PlanOp("resize", [x], [y], {
+            "mode": "nearest" if nd.op == "ResizeNearestNeighbor"
+            else "bilinear",
+            "align_corners": align, "half_pixel_centers": half,
+            "in_hw": (H, W), "out_hw": (Ho, Wo)}))
+
+    def lower_conv_transpose(self, nd: g.NodeDef, out: str) -> None:
+        """Conv2DBackpropInput (Keras Conv2DTranspose), NHWC, dilation 1:
+            y[n, i*sh-pt+r, j*sw-pl+s, co] += x[n,i,j,ci] * w[r,s,co,ci]
+        with (pt, pl) the pads of the forward conv it is the gradient of.
+        Two lowerings, both on weights rewritten here:
+          (a) kernel == stride, no padding, no residual (U-Net 2x2/s2):
+              output pixels do not overlap, so it is one gemm
+              [B*h*w, Cin] x [Cin, R*S*Cout] followed by a transpose of
+              the [B,h,w,R,S,Cout] view into [B,h,R,w,S,Cout];
+          (b) otherwise: zero_insert (x at the strided positions of a
+              zero image) then a stride-1 conv2d with the flipped,
+              in/out-swapped filter.
+        BiasAdd / BN / activation (and for (b) a residual add) fold into
+        the gemm / conv epilogue."""
+        if len(nd.input) != 3:
+            raise PlanError("Conv2DBackpropInput needs 3 inputs")
+        if _attr_s(nd, "data_format", "NHWC") != "NHWC":
+            raise PlanError("only NHWC Conv2DBackpropInput supported")
+        dil = _attr_ints(nd, "dilations") or [1, 1, 1, 1]
+        if any(d != 1 for d in dil):
+            raise PlanError(
+                f"dilated Conv2DBackpropInput unsupported ({dil})")
+        padding = _attr_s(nd, "padding", "SAME")
+        if padding not in ("SAME", "VALID"):
+            raise PlanError(
+                f"Conv2DBackpropInput padding {padding} unsupported")
+        sizes = self.const_value(nd.input[0])
+        if sizes is None:
+            raise PlanError("dynamic Conv2DBackpropInput input_sizes "
+                            "unsupported")
+        sizes = np.asarray(sizes).reshape(-1)
+        if sizes.size != 4:
+            raise PlanError("Conv2DBackpropInput input_sizes must be "
+                            f"[N,H,W,C] (got {sizes.tolist()})")
+        H, W, Cout = int(sizes[1]), int(sizes[2]), int(sizes[3])
+        w = np.asarray(self.weight_of(nd.input[1]), dtype=np.float32)
+        if w.ndim != 4:
+            raise PlanError("Conv2DBackpropInput filter must be rank 4")
+        R, S, Kc, Cin = w.shape                        # [R,S,Cout,Cin]
+        x = self.tid(nd.input[2])
+        xt = self.tensors[x]
+        xs = xt.shape
+        if len(xs) != 4 or xt.dtype != "f32" or \
+                any(is_sym(d) for d in xs[1:]):
+            raise PlanError("Conv2DBackpropInput needs an f32 [B,h,w,C] "
+                            "input with concrete h, w, C")
+        h, w_in = int(xs[1]), int(xs[2])
+        if int(xs[3]) != Cin or Kc != Cout:
+            raise PlanError(
+                f"Conv2DBackpropInput channels: filter {w.shape}, x "
+                f"{xs}, input_sizes {sizes.tolist()}")
+        strides = _attr_ints(nd, "strides") or [1, 1, 1, 1]
+        sh, sw = strides[1], strides[2]
+        if padding == "SAME":
+            eh, ew = math.ceil(H / sh), math.ceil(W / sw)
+            pad_h = max((eh - 1) * sh + R - H, 0)
+            pad_w = max((ew - 1) * sw + S - W, 0)
+            pt, pl = pad_h // 2, pad_w // 2
+        else:
+            eh, ew = (H - R) // sh + 1, (W - S) // sw + 1
+            pt = pl = 0
+        if H < 1 or W < 1 or (h, w_in) != (eh, ew):
+            raise PlanError(
+                f"Conv2DBackpropInput: input_sizes {sizes.tolist()} is "
+                f"inconsistent with x {h}x{w_in} ({padding}, stride "
+                f"{sh}x{sw}, filter {R}x{S} expects {eh}x{ew})")
+
+        bias, bn, residual, act, final = self._absorb_act_chain(nd)
+        if bn is not None:
+            scale, offset, mean, var, eps = bn
+            g_ = scale / np.sqrt(var + eps)
+            w = w * g_.reshape(1, 1, Cout, 1)
+            base = bias if bias is not None else np.zeros(Cout, np.float32)
+            bias = (base - mean) * g_ + offset
+        if bias is None:
+            bias = np.zeros(Cout, np.float32)
+        out_name = f"{final.name}:0"
+
+        if self.DECONV_GEMM_LOWERING and \
+                R == sh and S == sw and pt == 0 and pl == 0 and \
+                H == h * sh and W == w_in * sw and residual is None:
+            w_id = self.new_tensor(
+                (Cin, R * S * Cout), "f32", "weight", f"{nd.name}/gemm_w",
+                weight=np.ascontiguousarray(
+                    w.transpose(3, 0, 1, 2).reshape(Cin, -1)))
+            b_id = self.new_tensor((R * S * Cout,), "f32", "weight",
+                                   f"{nd.name}/gemm_b",
+                                   weight=np.tile(bias, R * S))
+            y6 = self.new_tensor((xs[0], h, w_in, R, S, Cout), "f32",
+                                 "activation", f"{nd.name}/taps:0")
+            self.ops.append(PlanOp("gemm", [x, w_id, b_id], [y6],
+                                   {"trans_a": False, "trans_b": False,
+                                    "act": act, "has_bias": True}))
+            yt = self.new_tensor((xs[0], h, R, w_in, S, Cout), "f32",
+                                 "activation", f"{nd.name}/interleaved:0")
+            self.ops.append(PlanOp("transpose", [y6], [yt],
+                                   {"perm": [0, 1, 3, 2, 4, 5]}))
+            y = self.new_tensor((xs[0], H, W, Cout), "f32", "activation",
+                                out_name, alias_of=yt)
+        else:
+            z, Hz, Wz = x, h, w_in
+            if (sh, sw) != (1, 1):
+                Hz, Wz = (h - 1) * sh + 1, (w_in - 1) * sw + 1
+                z = self.new_tensor((xs[0], Hz, Wz, Cin), "f32",
+                                    "activation", f"{nd.name}/zero_insert:0")
+                self.ops.append(PlanOp("zero_insert", [x], [z], {
+                    "stride": (sh, sw), "hw": (h, w_in),
+                    "out_hw": (Hz, Wz)}))
+            wf = np.ascontiguousarray(
+                w[::-1, ::-1].transpose(0, 1, 3, 2))       # [R,S,Cin,Cout]
+            w_id = self.new_tensor(tuple(wf.shape), "f32", "weight",
+                                   f"{nd.name}/fused_w", weight=wf)
+            b_id = self.new_tensor((Cout,), "f32", "weight",
+                                   f"{nd.name}/fused_b", weight=bias)
+            # top/left pads mirror the forward conv's; bottom/right are
+            # whatever makes the stride-1 conv produce exactly H x W
+            p_top, p_left = R - 1 - pt, S - 1 - pl
+            pads = (p_top, H + R - 1 - Hz - p_top,
+                    p_left, W + S - 1 - Wz - p_left)
+            y = self.new_tensor((xs[0], H, W, Cout), "f32", "activation",
+                                out_name)
+            inputs = [z, w_id, b_id]
+            params = {"stride": (1, 1), "pads": pads, "act": act,
+                      "rsck": (R, S, Cin, Cout), "hw": (Hz, Wz),
+                      "out_hw": (H, W)}
+            if residual is not None:
+                inputs.append(self.tid(residual))
+                params["residual"] = True
+            self.ops.append(PlanOp("conv2d", inputs, [y], params))
         if out_name != out:
             self.by_name[out] = y
 

@@ -273,6 +273,132 @@ def build_mobilenet_v2(image_size=224, num_classes=1000, seed=0,
 
 
 # ---------------------------------------------------------------------------
+# U-Net (inference): two-level encoder-decoder with skip connections —
+# the upsampling model family (segmentation heads, FPN necks,
+# autoencoder decoders). conv+BN+ReLU throughout; the decoder upsamples
+# by Conv2DBackpropInput (Keras Conv2DTranspose) or by an image resize
+# (Keras UpSampling2D, half_pixel_centers like TF2).
+# ---------------------------------------------------------------------------
+def build_unet(image_size=64, in_ch=3, base=16, num_classes=4,
+               upsample="deconv", seed=0):
+    """upsample: "deconv" (2x2/s2 VALID-shaped transposed conv for the
+    first decoder stage, 3x3/s2 SAME for the second — both planner
+    lowerings), "nearest" or "bilinear". image_size must be a multiple
+    of 4."""
+    if upsample not in ("deconv", "nearest", "bilinear"):
+        raise ValueError(f"unknown upsample {upsample!r}")
+    if image_size % 4:
+        raise ValueError("image_size must be a multiple of 4")
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+    i32 = gb.a_type(3)
+
+    def bn_relu(name, x, c):
+        scale = gb.const(f"{name}/gamma",
+                         np.abs(rng.standard_normal(c)).astype(np.float32)
+                         * 0.5 + 0.5)
+        offset = gb.const(f"{name}/beta",
+                          (rng.standard_normal(c) * 0.1).astype(np.float32))
+        mean = gb.const(f"{name}/mean",
+                        (rng.standard_normal(c) * 0.1).astype(np.float32))
+        var = gb.const(f"{name}/var",
+                       np.abs(rng.standard_normal(c)).astype(np.float32)
+                       * 0.5 + 0.5)
+        h = gb.node("FusedBatchNormV3", f"{name}/bn",
+                    [x, scale, offset, mean, var], T=f32, U=f32,
+                    epsilon=gb.a_float(1e-3),
+                    is_training=gb.a_bool(False),
+                    data_format=gb.a_str("NHWC"))
+        return gb.node("Relu", f"{name}/relu", [h], T=f32)
+
+    def conv(name, x, cin, cout, k=3):
+        w = gb.const(f"{name}/w", (rng.standard_normal((k, k, cin, cout))
+                                   * np.sqrt(2.0 / (k * k * cin))
+                                   ).astype(np.float32))
+        c = gb.node("Conv2D", f"{name}/conv", [x, w], T=f32,
+                    strides=gb.a_ints([1, 1, 1, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NHWC"))
+        return bn_relu(name, c, cout)
+
+    def pool(name, x):
+        return gb.node("MaxPool", name, [x], T=f32,
+                       ksize=gb.a_ints([1, 2, 2, 1]),
+                       strides=gb.a_ints([1, 2, 2, 1]),
+                       padding=gb.a_str("VALID"),
+                       data_format=gb.a_str("NHWC"))
+
+    def deconv(name, x, cin, cout, k, out_hw):
+        # input_sizes the way Keras Conv2DTranspose builds it:
+        # Pack([StridedSlice(Shape(x))[0], H, W, C])
+        shp = gb.node("Shape", f"{name}/shape", [x], T=f32, out_type=i32)
+        batch = gb.node(
+            "StridedSlice", f"{name}/batch",
+            [shp, gb.const(f"{name}/ss_b", np.array([0], np.int32)),
+             gb.const(f"{name}/ss_e", np.array([1], np.int32)),
+             gb.const(f"{name}/ss_s", np.array([1], np.int32))],
+            T=i32, Index=i32, shrink_axis_mask=gb.a_int(1))
+        sizes = gb.node(
+            "Pack", f"{name}/input_sizes",
+            [batch, gb.const(f"{name}/oh", np.int32(out_hw)),
+             gb.const(f"{name}/ow", np.int32(out_hw)),
+             gb.const(f"{name}/oc", np.int32(cout))],
+            T=i32, N=gb.a_int(4), axis=gb.a_int(0))
+        w = gb.const(f"{name}/w", (rng.standard_normal((k, k, cout, cin))
+                                   * np.sqrt(2.0 / (k * k * cin))
+                                   ).astype(np.float32))
+        d = gb.node("Conv2DBackpropInput", f"{name}/deconv",
+                    [sizes, w, x], T=f32,
+                    strides=gb.a_ints([1, 2, 2, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NHWC"))
+        return bn_relu(name, d, cout)
+
+    def resize(name, x, out_hw):
+        size = gb.const(f"{name}/size", np.array([out_hw, out_hw], np.int32))
+        op = "ResizeNearestNeighbor" if upsample == "nearest" \
+            else "ResizeBilinear"
+        return gb.node(op, name, [x, size], T=f32,
+                       align_corners=gb.a_bool(False),
+                       half_pixel_centers=gb.a_bool(True))
+
+    def up(name, x, cin, cout, k, out_hw):
+        if upsample == "deconv":
+            return deconv(name, x, cin, cout, k, out_hw)
+        return conv(f"{name}/conv", resize(f"{name}/resize", x, out_hw),
+                    cin, cout)
+
+    def concat(name, a, b):
+        axis = gb.const(f"{name}/axis", np.int32(3))
+        return gb.node("ConcatV2", name, [a, b, axis], T=f32,
+                       N=gb.a_int(2), Tidx=i32)
+
+    s = image_size
+    x = gb.placeholder("input", np.float32, [-1, s, s, in_ch],
+                       signature_name="input")
+    e1 = conv("enc1", x, in_ch, base)                       # s
+    e2 = conv("enc2", pool("pool1", e1), base, base * 2)    # s/2
+    bott = conv("bottleneck", pool("pool2", e2), base * 2, base * 4)  # s/4
+    u1 = up("up1", bott, base * 4, base * 2, 2, s // 2)
+    d1 = conv("dec1", concat("cat1", u1, e2), base * 4, base * 2)
+    u2 = up("up2", d1, base * 2, base, 3, s)
+    d2 = conv("dec2", concat("cat2", u2, e1), base * 2, base)
+    wh = gb.const("head/w", (rng.standard_normal((1, 1, base, num_classes))
+                             * np.sqrt(1.0 / base)).astype(np.float32))
+    bh = gb.const("head/b", np.zeros(num_classes, dtype=np.float32))
+    logits = gb.node("Conv2D", "head/conv", [d2, wh], T=f32,
+                     strides=gb.a_ints([1, 1, 1, 1]),
+                     padding=gb.a_str("SAME"),
+                     data_format=gb.a_str("NHWC"))
+    logits = gb.node("BiasAdd", "logits", [logits, bh], T=f32)
+    probs = gb.node("Softmax", "probs", [logits], T=f32)
+    gb.mark_output("probs", probs)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # BERT-base encoder (inference): embeddings -> 12 transformer layers ->
 # pooler. Frozen-graph decompositions for LayerNorm and GELU.
 # ---------------------------------------------------------------------------
@@ -435,6 +561,7 @@ _BUILDERS = {
     "resnet50": build_resnet50,
     "mobilenet_v2": build_mobilenet_v2,
     "bert_base": build_bert,
+    "unet": build_unet,
 }
 
 
