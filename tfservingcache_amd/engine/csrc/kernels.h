@@ -163,7 +163,8 @@ void launch_quant_rowwise(hipStream_t s, const ushort* x, uint8_t* q,
                           int64_t Kp);
 
 // Fused multi-head attention over the natural [B*S, H*D] QKV layout
-// (flash-style online softmax; D must be 64). See ops/attention.hip.
+// (flash-style online softmax; D must be 64 or 128, anything else
+// throws). See ops/attention.hip.
 // bias (nullable, bf16) is added to the scaled scores before the
 // softmax, read as bias[b*sb + h*sh + q*sq + kv] with strides in
 // elements; a 0 stride broadcasts that dimension ([B,1,1,S] key

@@ -16,8 +16,17 @@
 // __syncthreads covers 128 kv columns of MFMA work and the online
 // softmax runs once per 128 columns instead of per 64; the P bounce
 // region overlaps the (dead after the prologue) Q tile. 80 KB LDS ->
-// 2 workgroups/CU. Requires head_dim D == 64 (BERT-base class); the
-// planner keeps the unfused path otherwise.
+// 2 workgroups/CU.
+//
+// The head dim HD is a template parameter: 64 (BERT-base class) or 128
+// (decoder-style heads); the planner keeps the unfused path otherwise.
+// HD=128 doubles the row of the Q and K tiles (256 B, 16 chunks: the
+// P-bounce image), the rows of the V^T tile (128), the K=32 steps of
+// QK^T (4) and the O fragments (8); a kv tile is 32 KB instead of 16,
+// the Q tile exactly fills the 16 KB Q/P overlay. Its RING=2 variant
+// (80 KB, 2 workgroups/CU) serves every S: past one tile pair it
+// restages the two slots between pairs instead of prefetching into a
+// second pair of slots (a ring of 4 is 144 KB, one workgroup/CU).
 //
 // Optional additive bias (HAS_BIAS): the attention-mask term real
 // exports add to the scaled scores before the softmax,
@@ -38,6 +47,7 @@
 
 #include <climits>
 #include <stdexcept>
+#include <string>
 
 namespace tfsc {
 
@@ -47,11 +57,15 @@ using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
 using ushort2_t = __attribute__((ext_vector_type(2))) ushort;
 
-constexpr int D = 64;          // head dim
 constexpr int QBLK = 64;       // q rows per workgroup (16 per wave)
 constexpr int KVBLK = 64;      // kv rows per staged tile
 constexpr int NW = 4;          // waves
 constexpr int THREADS = NW * WAVE;
+// kv-tile slots of the HD=128 geometry: 2 (80 KB, 2 WG/CU, restage
+// between pairs) measured 63.7 us against 92.8 us for 4 (144 KB, 1
+// WG/CU, pair prefetch) at B=16, H=8, S=512; equal at S=128
+// (profiles/attention_hd128.md)
+constexpr int RING_HD128 = 2;
 
 // shared 64x64 bf16 tile image with the gemm.hip chunk-XOR swizzle
 TFSC_DEV int t_off(int row, int chunk) {
@@ -63,20 +77,30 @@ TFSC_DEV int p_off(int row, int chunk) {
   return row * 256 + ((chunk ^ (row & 7)) << 4);
 }
 
-// stage a [64][64] tile from rows of a [rows_total, H*D] matrix
-// (row = s index, stride ld elements, cols = one head's D slice)
+// Q / K tile image [64][HD]: t_off rows for HD=64, p_off rows for 128
+template <int HD>
+TFSC_DEV int qk_off(int row, int chunk) {
+  return HD == 64 ? t_off(row, chunk) : p_off(row, chunk);
+}
+
+// stage a [64][HD] tile from rows of a [rows_total, H*D] matrix
+// (row = s index, stride ld elements, cols = one head's D slice); one
+// wave instruction fills 1 KB of LDS = 8 rows (HD=64) or 4 (HD=128)
+template <int HD>
 TFSC_DEV void stage_rows_glds(const ushort* __restrict__ src, int64_t ld,
                               int row0, int row_limit, char* lds_tile,
                               int wave, int lane) {
-  int r_in = lane >> 3, chunk = lane & 7;
+  constexpr int LPR = HD / 8;          // lanes (16 B chunks) per row
+  constexpr int RPI = WAVE / LPR;      // rows per instruction
+  int r_in = lane / LPR, chunk = lane % LPR;
   #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row = wave * 16 + i * 8 + r_in;
+  for (int i = 0; i < 16 / RPI; ++i) {
+    int row = wave * 16 + i * RPI + r_in;
     int grow = row0 + row;
     grow = grow < row_limit ? grow : row_limit;
     int chunk_src = chunk ^ (row & 7);
     const ushort* gptr = src + (int64_t)grow * ld + chunk_src * 8;
-    char* lds_base = lds_tile + (wave * 16 + i * 8) * 128;
+    char* lds_base = lds_tile + (wave * 16 + i * RPI) * (HD * 2);
     __builtin_amdgcn_global_load_lds(
         reinterpret_cast<const uint32_t*>(gptr),
         reinterpret_cast<uint32_t*>(lds_base), 16, 0, 0);
@@ -108,10 +132,52 @@ TFSC_DEV void stage_vt(const ushort* __restrict__ src, int64_t ld,
   }
 }
 
+// stage V^T for HD=128: [128 d][64 kv] image (128 t_off rows) from V
+// rows [kv, H*D]. A thread takes two adjacent kv rows of one 8-wide d
+// group (two 16 B global reads) and writes 8 dwords, each the (kv,
+// kv+1) pair of one d row: half the LDS writes of the 2-byte scatter.
+// A wave covers 32 kv x 4 d groups per pass (64 B contiguous per row).
+TFSC_DEV void stage_vt128(const ushort* __restrict__ src, int64_t ld,
+                          int row0, int row_limit, char* lds_tile,
+                          int wave, int lane) {
+  int kv = (wave & 1) * 32 + (lane >> 2) * 2;       // even, 0..62
+  int gkv0 = row0 + kv, gkv1 = row0 + kv + 1;
+  gkv0 = gkv0 < row_limit ? gkv0 : row_limit;
+  gkv1 = gkv1 < row_limit ? gkv1 : row_limit;
+  #pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    int dg = (pass * 2 + (wave >> 1)) * 4 + (lane & 3);   // 0..15
+    short8_t v0 = *reinterpret_cast<const short8_t*>(
+        src + (int64_t)gkv0 * ld + dg * 8);
+    short8_t v1 = *reinterpret_cast<const short8_t*>(
+        src + (int64_t)gkv1 * ld + dg * 8);
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      int d = dg * 8 + j;
+      int byte_off = t_off(d, kv >> 3) + (kv & 7) * 2;
+      *reinterpret_cast<uint32_t*>(lds_tile + byte_off) =
+          uint32_t(ushort(v0[j])) | (uint32_t(ushort(v1[j])) << 16);
+    }
+  }
+}
+
+template <int HD>
+TFSC_DEV void stage_vt_hd(const ushort* __restrict__ src, int64_t ld,
+                          int row0, int row_limit, char* lds_tile,
+                          int wave, int lane) {
+  if constexpr (HD == 64)
+    stage_vt(src, ld, row0, row_limit,
+             reinterpret_cast<ushort*>(lds_tile), wave, lane);
+  else
+    stage_vt128(src, ld, row0, row_limit, lds_tile, wave, lane);
+}
+
 // RING = staged kv-tile slots: 4 (pair prefetch, 80 KB LDS, 2 WG/CU)
 // for long sequences; 2 (no prefetch needed when n_kv <= 2, 48 KB LDS,
-// 3 WG/CU) for the S <= 128 serving shapes
-template <int RING, bool HAS_BIAS>
+// 3 WG/CU) for the S <= 128 serving shapes. HD=128 launches RING_HD128
+// = 2 for every S (80 KB, 2 WG/CU), restaging its two slots between
+// pairs when n_kv > 2; its RING=4 form (144 KB) prefetches like HD=64.
+template <int HD, int RING, bool HAS_BIAS>
 __global__ __launch_bounds__(THREADS)
 void attention_kernel(const ushort* __restrict__ Q,
                       const ushort* __restrict__ K,
@@ -120,16 +186,19 @@ void attention_kernel(const ushort* __restrict__ Q,
                       int B, int S, int H, float scale, int n_qblk,
                       const ushort* __restrict__ bias, int64_t bias_sb,
                       int64_t bias_sh, int bias_sq) {
-  // LDS: K ring RINGx8KB | V^T ring RINGx8KB | q/p overlay 16 KB
-  // (q tile uses the first 8 KB until its registers are loaded; the
-  // per-wave [16][128] P bounce then reuses the whole 16 KB)
-  __shared__ __attribute__((aligned(16))) char smem[8192 * (2 * RING + 2)];
-  auto k_lds = [&](int buf) -> char* { return smem + buf * 8192; };
+  static_assert(HD == 64 || HD == 128, "head dim geometries");
+  constexpr int D = HD;
+  constexpr int TILE = KVBLK * HD * 2;   // one K or V^T tile: 8 / 16 KB
+  // LDS: K ring RINGxTILE | V^T ring RINGxTILE | q/p overlay 16 KB
+  // (q tile uses the first 64*HD*2 B until its registers are loaded;
+  // the per-wave [16][128] P bounce then reuses the whole 16 KB)
+  __shared__ __attribute__((aligned(16))) char smem[TILE * 2 * RING + 16384];
+  auto k_lds = [&](int buf) -> char* { return smem + buf * TILE; };
   auto vt_lds = [&](int buf) -> char* {
-    return smem + RING * 8192 + buf * 8192;
+    return smem + RING * TILE + buf * TILE;
   };
-  char* q_lds = smem + 2 * RING * 8192;
-  char* p_lds = smem + 2 * RING * 8192;  // 4 waves x 4 KB (after Q)
+  char* q_lds = smem + 2 * RING * TILE;
+  char* p_lds = smem + 2 * RING * TILE;  // 4 waves x 4 KB (after Q)
 
   const int flat = blockIdx.x;
   const int qb = flat % n_qblk;
@@ -150,20 +219,18 @@ void attention_kernel(const ushort* __restrict__ Q,
   // ---- stage Q AND the first kv tile pair concurrently (disjoint
   // LDS; one barrier covers all five tiles), then pull this wave's 16
   // q rows into registers
-  stage_rows_glds(Qb, ld, q0, S - 1, q_lds, wave, lane);
-  stage_rows_glds(Kb, ld, 0, S - 1, k_lds(0), wave, lane);
-  stage_vt(Vb, ld, 0, S - 1, reinterpret_cast<ushort*>(vt_lds(0)), wave,
-           lane);
-  stage_rows_glds(Kb, ld, KVBLK, S - 1, k_lds(1), wave, lane);
-  stage_vt(Vb, ld, KVBLK, S - 1, reinterpret_cast<ushort*>(vt_lds(1)),
-           wave, lane);
+  stage_rows_glds<HD>(Qb, ld, q0, S - 1, q_lds, wave, lane);
+  stage_rows_glds<HD>(Kb, ld, 0, S - 1, k_lds(0), wave, lane);
+  stage_vt_hd<HD>(Vb, ld, 0, S - 1, vt_lds(0), wave, lane);
+  stage_rows_glds<HD>(Kb, ld, KVBLK, S - 1, k_lds(1), wave, lane);
+  stage_vt_hd<HD>(Vb, ld, KVBLK, S - 1, vt_lds(1), wave, lane);
   __syncthreads();
-  bf16x8_t qf[2];      // A-fragments for the 2 K=32 steps over D
+  bf16x8_t qf[D / 32];  // A-fragments for the K=32 steps over D
   #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
+  for (int ks = 0; ks < D / 32; ++ks) {
     int row = wave * 16 + frow;
     qf[ks] = *reinterpret_cast<const bf16x8_t*>(
-        q_lds + t_off(row, ks * 4 + kgrp));
+        q_lds + qk_off<HD>(row, ks * 4 + kgrp));
   }
   __syncthreads();   // q_lds consumed; the region becomes the P bounce
 
@@ -172,7 +239,7 @@ void attention_kernel(const ushort* __restrict__ Q,
   // keys) or -3.0e38 (kv tail); the running max then starts ABOVE the
   // tail sentinel so those columns exponentiate to 0, not exp(0).
   float m_run[4], l_run[4];
-  f32x4_t o_acc[4] = {};      // O fragments over d (4 x 16 cols)
+  f32x4_t o_acc[D / 16] = {}; // O fragments over d (16 cols each)
   #pragma unroll
   for (int r = 0; r < 4; ++r) {
     m_run[r] = HAS_BIAS ? -1.0e38f : -3.0e38f;
@@ -203,6 +270,18 @@ void attention_kernel(const ushort* __restrict__ Q,
     // pair 0 was staged with Q (covered by the prologue barriers); a
     // barrier here covers the pair t prefetch issued in iteration t-1
     if (t > 0) __syncthreads();
+    if (HD == 128 && RING < 4 && t > 0) {
+      // ring of 2 past the first pair: every wave is done with pair
+      // t-1 (barrier above); restage both slots, then a second barrier
+      stage_rows_glds<HD>(Kb, ld, 2 * t * KVBLK, S - 1, k_lds(0), wave,
+                          lane);
+      stage_vt_hd<HD>(Vb, ld, 2 * t * KVBLK, S - 1, vt_lds(0), wave, lane);
+      stage_rows_glds<HD>(Kb, ld, (2 * t + 1) * KVBLK, S - 1, k_lds(1),
+                          wave, lane);
+      stage_vt_hd<HD>(Vb, ld, (2 * t + 1) * KVBLK, S - 1, vt_lds(1), wave,
+                      lane);
+      __syncthreads();
+    }
     const int base = RING >= 4 ? (t & 1) * 2 : 0;  // slots of this pair
     const int kv_base = t * 2 * KVBLK;
     // bias for this lane's 8 kv columns x 4 q rows, issued ahead of
@@ -242,14 +321,14 @@ void attention_kernel(const ushort* __restrict__ Q,
     }
     if (RING >= 4 && t + 1 < n_pair) {
       const int nb = ((t + 1) & 1) * 2;
-      stage_rows_glds(Kb, ld, (2 * t + 2) * KVBLK, S - 1, k_lds(nb),
+      stage_rows_glds<HD>(Kb, ld, (2 * t + 2) * KVBLK, S - 1, k_lds(nb),
+                          wave, lane);
+      stage_vt_hd<HD>(Vb, ld, (2 * t + 2) * KVBLK, S - 1, vt_lds(nb), wave,
+                      lane);
+      stage_rows_glds<HD>(Kb, ld, (2 * t + 3) * KVBLK, S - 1,
+                          k_lds(nb + 1), wave, lane);
+      stage_vt_hd<HD>(Vb, ld, (2 * t + 3) * KVBLK, S - 1, vt_lds(nb + 1),
                       wave, lane);
-      stage_vt(Vb, ld, (2 * t + 2) * KVBLK, S - 1,
-               reinterpret_cast<ushort*>(vt_lds(nb)), wave, lane);
-      stage_rows_glds(Kb, ld, (2 * t + 3) * KVBLK, S - 1, k_lds(nb + 1),
-                      wave, lane);
-      stage_vt(Vb, ld, (2 * t + 3) * KVBLK, S - 1,
-               reinterpret_cast<ushort*>(vt_lds(nb + 1)), wave, lane);
     }
 
     // ---- QK^T: scores[16 q rows][128 kv] = 8 x 1x4 fragments
@@ -258,11 +337,11 @@ void attention_kernel(const ushort* __restrict__ Q,
     for (int half = 0; half < 2; ++half) {
       const char* kt = k_lds(base + half);
       #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
+      for (int ks = 0; ks < D / 32; ++ks) {
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(
-              kt + t_off(ni * 16 + frow, ks * 4 + kgrp));
+              kt + qk_off<HD>(ni * 16 + frow, ks * 4 + kgrp));
           sc[half * 4 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               qf[ks], kf, sc[half * 4 + ni], 0, 0, 0);
         }
@@ -317,7 +396,7 @@ void attention_kernel(const ushort* __restrict__ Q,
     }
     // rescale O by alpha (rows of O fragments match reg index)
     #pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
+    for (int ni = 0; ni < D / 16; ++ni)
       #pragma unroll
       for (int r = 0; r < 4; ++r)
         o_acc[ni][r] *= alpha[r];
@@ -345,7 +424,7 @@ void attention_kernel(const ushort* __restrict__ Q,
         const char* vt = vt_lds(base + (ks >> 1));
         int ksub = ks & 1;
         #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
+        for (int ni = 0; ni < D / 16; ++ni) {
           bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(
               vt + t_off(ni * 16 + frow, ksub * 4 + kgrp));
           o_acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -363,47 +442,55 @@ void attention_kernel(const ushort* __restrict__ Q,
     float inv = l_run[r] > 0.f ? 1.f / l_run[r] : 0.f;
     ushort* orow = Ob + (int64_t)row * ld;
     #pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
+    for (int ni = 0; ni < D / 16; ++ni)
       orow[ni * 16 + frow] = f2bf(o_acc[ni][r] * inv);
   }
 }
 
 }  // namespace attn
 
+template <int HD, int RING>
+static void launch_geometry(hipStream_t s, dim3 grid, const ushort* Q,
+                            const ushort* K, const ushort* V, ushort* O,
+                            int B, int S, int H, float scale, int n_qblk,
+                            const ushort* bias, int64_t bias_sb,
+                            int64_t bias_sh, int bias_sq) {
+  dim3 block(attn::THREADS);
+  if (!bias)
+    // unmasked models: the same instantiations as ever
+    hipLaunchKernelGGL((attn::attention_kernel<HD, RING, false>), grid,
+                       block, 0, s, Q, K, V, O, B, S, H, scale, n_qblk,
+                       nullptr, 0, 0, 0);
+  else
+    hipLaunchKernelGGL((attn::attention_kernel<HD, RING, true>), grid,
+                       block, 0, s, Q, K, V, O, B, S, H, scale, n_qblk,
+                       bias, bias_sb, bias_sh, bias_sq);
+}
+
 void launch_attention(hipStream_t s, const ushort* Q, const ushort* K,
                       const ushort* V, ushort* O, int B, int S, int H,
                       int D_, float scale, const ushort* bias,
                       int64_t bias_sb, int64_t bias_sh, int64_t bias_sq) {
-  if (D_ != attn::D)
-    throw std::runtime_error("fused attention requires head_dim == 64");
+  if (D_ != 64 && D_ != 128)
+    throw std::runtime_error(
+        "fused attention requires head_dim 64 or 128, got " +
+        std::to_string(D_));
   // the kernel indexes one (b, h) bias plane with 32-bit offsets
   if (bias && (bias_sb < 0 || bias_sh < 0 || bias_sq < 0 ||
                (int64_t)(S - 1) * bias_sq + S > INT32_MAX))
     throw std::runtime_error("fused attention: bad bias strides");
   int n_qblk = (S + attn::QBLK - 1) / attn::QBLK;
   dim3 grid(B * H * n_qblk);
-  dim3 block(attn::THREADS);
-  const bool small = S <= 2 * attn::KVBLK;
   const int sq = int(bias_sq);
-  if (!bias) {
-    // unmasked models: the same two instantiations as ever
-    if (small)
-      hipLaunchKernelGGL((attn::attention_kernel<2, false>), grid, block,
-                         0, s, Q, K, V, O, B, S, H, scale, n_qblk,
-                         nullptr, 0, 0, 0);
-    else
-      hipLaunchKernelGGL((attn::attention_kernel<4, false>), grid, block,
-                         0, s, Q, K, V, O, B, S, H, scale, n_qblk,
-                         nullptr, 0, 0, 0);
-  } else if (small) {
-    hipLaunchKernelGGL((attn::attention_kernel<2, true>), grid, block, 0,
-                       s, Q, K, V, O, B, S, H, scale, n_qblk, bias,
-                       bias_sb, bias_sh, sq);
-  } else {
-    hipLaunchKernelGGL((attn::attention_kernel<4, true>), grid, block, 0,
-                       s, Q, K, V, O, B, S, H, scale, n_qblk, bias,
-                       bias_sb, bias_sh, sq);
-  }
+  if (D_ == 128)
+    launch_geometry<128, attn::RING_HD128>(s, grid, Q, K, V, O, B, S, H, scale, n_qblk,
+                            bias, bias_sb, bias_sh, sq);
+  else if (S <= 2 * attn::KVBLK)
+    launch_geometry<64, 2>(s, grid, Q, K, V, O, B, S, H, scale, n_qblk,
+                           bias, bias_sb, bias_sh, sq);
+  else
+    launch_geometry<64, 4>(s, grid, Q, K, V, O, B, S, H, scale, n_qblk,
+                           bias, bias_sb, bias_sh, sq);
 }
 
 }  // namespace tfsc

@@ -1622,8 +1622,8 @@ def fuse_attention(plan: Plan) -> Plan:
     exports ((1 - mask) * -10000 as [B,1,1,S], or a constant [1,1,S,S]
     causal bias); it becomes a 4th input plus `bias_dims` (see
     _attention_bias_dims) and may be shared by every layer. Fused only
-    when head_dim == 64 (the kernel's constraint) and the bias is
-    eligible; otherwise left as-is."""
+    when head_dim is 64 or 128 (the kernel's two geometries) and the
+    bias is eligible; otherwise left as-is."""
     ops = plan.ops
     produced_by: Dict[int, int] = {}
     for oi, op in enumerate(ops):
@@ -1677,7 +1677,7 @@ def fuse_attention(plan: Plan) -> Plan:
             scale = 1.0 / scale
         q4d, k4d = tq.inputs[0], tk.inputs[0]
         shape = plan.tensors[q4d].shape        # [B, S, H, D]
-        if len(shape) != 4 or shape[3] != 64:
+        if len(shape) != 4 or shape[3] not in (64, 128):
             continue
         # optional additive bias (attention mask) on the scaled scores
         sm_oi = sole_consumer(mul_op.outputs[0])
