@@ -43,12 +43,10 @@ void launch_layernorm(hipStream_t s, const ushort* x, const ushort* gamma,
                       int64_t cols, float eps);
 void launch_reduce_mean_last(hipStream_t s, const ushort* x, ushort* y,
                              int64_t rows, int64_t cols);
-// mean over axis 1 of [d0, d1, d2]
+// mean over axis 1 of [d0, d1, d2] (global mean over H,W of NHWC is
+// d1 = H*W)
 void launch_reduce_mean_mid(hipStream_t s, const ushort* x, ushort* y,
                             int64_t d0, int64_t d1, int64_t d2);
-// global mean over H,W of NHWC
-void launch_global_mean(hipStream_t s, const ushort* x, ushort* y,
-                        int64_t n, int64_t hw, int64_t c);
 void launch_pool(hipStream_t s, const ushort* x, ushort* y, bool is_max,
                  int N, int H, int W, int C, int Ho, int Wo, int kh, int kw,
                  int sh, int sw, int pt, int pl);

@@ -360,11 +360,6 @@ void launch_reduce_mean_mid(hipStream_t s, const ushort* x, ushort* y,
                      x, y, d0, d1, d2);
 }
 
-void launch_global_mean(hipStream_t s, const ushort* x, ushort* y,
-                        int64_t n, int64_t hw, int64_t c) {
-  launch_reduce_mean_mid(s, x, y, n, hw, c);
-}
-
 // ---------------------------------------------------------------------------
 // pooling (NHWC; one thread per output element, coalesced over C)
 // ---------------------------------------------------------------------------

@@ -1,0 +1,601 @@
+"""Call emission: (Plan, batch bucket, dtype) -> relocatable call template.
+
+Pure Python over the plan: no torch, no GPU, no extension. Every pointer
+a kernel call takes is written as a descriptor, never an address:
+
+    None                    null pointer
+    (WS, byte offset)       into the context's workspace arena
+    (region key, offset)    into a weight region of the model, where the
+                            key is one of
+        ("blob",)                   bf16 master blob (see blob_layout)
+        ("int", idx)                int32 weight tensor idx
+        ("gw", idx, trans_b)        pre-transposed GEMM weight
+        ("cw", idx)                 conv weight [Kc][pad64(R*S*C)]
+        ("cw", idx, "cpad", c8)     conv weight, input channels widened
+        ("f8q"|"f8s", idx, trans_b) fp8 GEMM weight bytes / row scales
+        ("zeros",)                  small zeroed buffer (conv gather)
+
+engine/gpu.py resolves each region key to a device base address (from
+the transform arena, or by materialising the transform) and rebases the
+calls in one C++ call. Call kinds are carried by name ("GEMM" for the
+extension's K_GEMM); the numeric enum lives in csrc/executor.cpp only.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from .planner import Plan, PlanOp
+
+ALIGN = 256  # byte alignment of workspace slices
+
+WS = ("ws",)        # descriptor key of the workspace arena
+
+# every call kind emission can produce (names of the extension's K_*)
+KINDS = frozenset({
+    "ELT_UNARY", "ELT_BINARY", "BN_ACT", "SOFTMAX", "LAYERNORM",
+    "MEAN_LAST", "MEAN_MID", "POOL", "TRANSPOSE", "GATHER", "PAD_NHWC",
+    "GEMM", "BGEMM", "CONV", "PAD_LAST", "ATTENTION", "DEPTHWISE",
+    "GEMM_FP8", "QUANT_FP8", "CAST", "ARGMAX_LAST", "SCATTER", "RESIZE",
+    "ZERO_INSERT",
+})
+
+# plan ops that are one [rows, cols] kernel over the last axis
+_ROWWISE = {"softmax": "SOFTMAX", "reduce_mean_last": "MEAN_LAST",
+            "argmax_last": "ARGMAX_LAST"}
+
+_ACT_CODE = {"none": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "gelu": 4,
+             "relu6": 5}
+
+_ELT_CODE = {
+    "add": 0, "sub": 1, "mul": 2, "div": 3, "max": 4, "min": 5,
+    "sqdiff": 6, "relu": 7, "tanh": 8, "sigmoid": 9, "erf": 10,
+    "sqrt": 11, "rsqrt": 12, "exp": 13, "neg": 14, "square": 15,
+    "gelu": 16, "relu6": 17,
+}
+
+
+def _pad64(k: int) -> int:
+    return (k + 63) // 64 * 64
+
+
+def _pad128(k: int) -> int:
+    return (k + 127) // 128 * 128
+
+
+def _pad256b(n: int) -> int:
+    return (n + 255) // 256 * 256
+
+
+def _numel(shape) -> int:
+    return int(np.prod(shape)) if shape else 1
+
+
+def _rows_cols(shape) -> List[int]:
+    return [_numel(shape[:-1]), shape[-1]]
+
+
+def _strides(shape) -> List[int]:
+    """Element strides of a contiguous tensor."""
+    st = [1] * len(shape)
+    for d in range(len(shape) - 2, -1, -1):
+        st[d] = st[d + 1] * shape[d + 1]
+    return st
+
+
+def _act(p: dict) -> int:
+    return _ACT_CODE[p.get("act", "none")]
+
+
+def _off(desc, nbytes: int):
+    """desc + nbytes (a pointer into the middle of a buffer)."""
+    return (desc[0], desc[1] + nbytes)
+
+
+@dataclass
+class _BufInfo:
+    offset: int = -1          # byte offset in workspace
+    nbytes: int = 0
+    shape: Tuple[int, ...] = ()
+    is_int: bool = False
+
+
+@dataclass
+class BlobLayout:
+    """Where each weight of a plan lives on the device: float weights
+    at an element offset of one bf16 master blob (each slot rounded up
+    to 128 elements, which keeps 256-byte alignment), integer weights as
+    int32 tensors of their own."""
+    slots: Dict[int, Tuple[int, int]]    # tensor idx -> (elem off, n)
+    total: int                           # blob length in bf16 elements
+    int_idx: List[int]
+
+
+# dtype objects: comparing a dtype with a scalar type builds a dtype per
+# comparison, and blob_layout runs on every model load
+_INT_DTYPES = (np.dtype(np.int32), np.dtype(np.int64))
+
+
+def blob_layout(plan: Plan) -> BlobLayout:
+    slots: Dict[int, Tuple[int, int]] = {}
+    int_idx: List[int] = []
+    total = 0
+    for t in plan.tensors:
+        if t.kind != "weight" or t.weight is None:
+            continue
+        if t.weight.dtype in _INT_DTYPES:
+            int_idx.append(t.idx)
+        else:
+            n = int(t.weight.size)
+            slots[t.idx] = (total, n)
+            total += _pad128(n)
+    return BlobLayout(slots, total, int_idx)
+
+
+@dataclass
+class Template:
+    """Everything a context of one (plan, bucket, dtype) needs besides
+    device memory."""
+    shapes: List[Tuple[int, ...]]
+    root: List[int]                      # alias chains resolved
+    bufs: Dict[int, _BufInfo]            # root idx -> workspace slice
+    total_bytes: int                     # workspace size
+    scratch_off: Dict[int, int]          # op idx -> scratch byte offset
+    region_keys: List[tuple]             # in order of first use
+    calls: List[tuple]                   # (kind, descs, ints, floats)
+
+
+def build_template(plan: Plan, batch: int, dtype: str) -> Template:
+    e = _Emitter(plan, batch, dtype)
+    e.plan_buffers()
+    e.emit_calls()
+    return Template(e.shapes, e.root, e.bufs, e.total_bytes,
+                    e.scratch_off, e.region_keys, e.calls)
+
+
+class _Emitter:
+    def __init__(self, plan: Plan, batch: int, dtype: str):
+        self.plan = plan
+        self.batch = batch
+        self.dtype = dtype
+        self.layout = blob_layout(plan)
+        self.shapes: List[Tuple[int, ...]] = [
+            plan.resolve_shape(t.shape, batch) for t in plan.tensors]
+        self.root = [t.alias_of if t.alias_of is not None else t.idx
+                     for t in plan.tensors]
+        # resolve alias chains
+        for i, r in enumerate(self.root):
+            seen = 0
+            while plan.tensors[r].alias_of is not None and seen < 16:
+                r = plan.tensors[r].alias_of
+                seen += 1
+            self.root[i] = r
+        self.region_keys: List[tuple] = []
+        self._seen = set()
+        self.calls: List[tuple] = []
+
+    # -- buffer planning ---------------------------------------------------
+    def _buf_bytes(self, idx: int) -> int:
+        esize = 4 if self.plan.tensors[idx].dtype == "i32" else 2
+        return max(_numel(self.shapes[idx]) * esize, esize)
+
+    def plan_buffers(self) -> None:
+        plan = self.plan
+        root = self.root
+        live_end: Dict[int, int] = {}
+        scratch_sizes: Dict[int, int] = {}   # op_idx -> scratch bytes
+
+        n_ops = len(plan.ops)
+        for oi, op in enumerate(plan.ops):
+            for i in op.inputs + op.outputs:
+                live_end[root[i]] = oi
+        for i in plan.sig_outputs.values():
+            live_end[root[i]] = n_ops + 1
+        for i in plan.sig_inputs.values():
+            live_end[root[i]] = max(live_end.get(root[i], -1), 0)
+
+        # scratch sizes (conv channel-pad, gemm K-pad)
+        for oi, op in enumerate(plan.ops):
+            if op.kind == "gemm":
+                a_shape = self.shapes[op.inputs[0]]
+                K = a_shape[-1]
+                M = int(np.prod(a_shape[:-1]))
+                if self.dtype == "fp8":
+                    # quantized activations (u8 [M, Kp128]) + row scales
+                    Kp = _pad128(K)
+                    scratch_sizes[oi] = _pad256b(M * Kp) + M * 4
+                elif K % 64 != 0:
+                    scratch_sizes[oi] = M * _pad64(K) * 2
+            if op.kind == "conv2d":
+                R, S, Cin, Kc = op.params["rsck"]
+                is_1x1 = (R == 1 and S == 1 and
+                          op.params["stride"] == (1, 1) and
+                          op.params["pads"] == (0, 0, 0, 0) and
+                          Cin % 64 == 0)
+                # channel-pad scratch for the C%8!=0 case (RGB stem):
+                # input widened to C8 channels, then fused conv
+                if not is_1x1 and Cin % 8 != 0:
+                    H, W = op.params["hw"]
+                    c8 = (Cin + 7) // 8 * 8
+                    scratch_sizes[oi] = self.batch * H * W * c8 * 2
+
+        self.bufs: Dict[int, _BufInfo] = {}
+        self.scratch_off: Dict[int, int] = {}
+        free: List[Tuple[int, int]] = []     # (nbytes, offset)
+        cursor = 0
+
+        def alloc(nbytes: int) -> int:
+            nonlocal cursor
+            nbytes = (nbytes + ALIGN - 1) // ALIGN * ALIGN
+            best = None
+            for j, (sz, off) in enumerate(free):
+                if sz >= nbytes and (best is None or sz < free[best][0]):
+                    best = j
+            if best is not None:
+                sz, off = free.pop(best)
+                if sz > nbytes:
+                    free.append((sz - nbytes, off + nbytes))
+                return off
+            off = cursor
+            cursor += nbytes
+            return off
+
+        def release(off: int, nbytes: int) -> None:
+            nbytes = (nbytes + ALIGN - 1) // ALIGN * ALIGN
+            free.append((nbytes, off))
+
+        def ensure(idx: int) -> None:
+            r = root[idx]
+            if r in self.bufs:
+                return
+            nb = self._buf_bytes(r)
+            self.bufs[r] = _BufInfo(alloc(nb), nb, self.shapes[r],
+                                    plan.tensors[r].dtype == "i32")
+
+        # inputs first (persistent through the run)
+        for i in plan.sig_inputs.values():
+            ensure(i)
+        for oi, op in enumerate(plan.ops):
+            for i in op.outputs:
+                ensure(i)
+            if oi in scratch_sizes:
+                self.scratch_off[oi] = alloc(scratch_sizes[oi])
+                release(self.scratch_off[oi], scratch_sizes[oi])
+                # NOTE: scratch freed immediately after alloc so the NEXT
+                # op's outputs can reuse it; but it must survive through
+                # this op — handled because outputs were allocated first.
+            for i in op.inputs:
+                r = root[i]
+                if r in self.bufs and live_end.get(r, -1) == oi and \
+                        plan.tensors[r].kind != "input" and \
+                        live_end[r] <= n_ops:
+                    release(self.bufs[r].offset, self.bufs[r].nbytes)
+        self.total_bytes = max(cursor, ALIGN)
+
+    # -- pointer descriptors -----------------------------------------------
+    def _weight(self, idx: int):
+        """Master copy of weight tensor idx (no alias resolution)."""
+        slot = self.layout.slots.get(idx)
+        if slot is not None:
+            return (("blob",), slot[0] * 2)
+        if idx in self.layout.int_idx:
+            return (("int", idx), 0)
+        raise KeyError(idx)
+
+    def _ptr(self, idx: int):
+        r = self.root[idx]
+        if self.plan.tensors[r].kind == "weight":
+            return self._weight(r)
+        return (WS, self.bufs[r].offset)
+
+    def _io(self, op: PlanOp, n_in: int) -> list:
+        """The op's first n_in inputs, then its output."""
+        return [self._ptr(i) for i in op.inputs[:n_in]] + \
+            [self._ptr(op.outputs[0])]
+
+    def _scratch(self, oi: int):
+        return (WS, self.scratch_off[oi])
+
+    def _weight_shape(self, idx: int) -> Optional[Tuple[int, ...]]:
+        """Shape of a constant weight operand, None for an activation."""
+        if idx in self.layout.slots or idx in self.layout.int_idx:
+            return tuple(self.plan.tensors[idx].weight.shape)
+        return None
+
+    def _call(self, kind: str, ptrs: list, ints: list,
+              floats: Optional[list] = None) -> None:
+        assert kind in KINDS, kind
+        for d in ptrs:
+            if d is not None and d[0] != WS and d[0] not in self._seen:
+                self._seen.add(d[0])
+                self.region_keys.append(d[0])
+        self.calls.append((kind, ptrs, ints, floats or []))
+
+    # -- call emission -----------------------------------------------------
+    def emit_calls(self) -> None:
+        call, io = self._call, self._io
+        for oi, op in enumerate(self.plan.ops):
+            k, p = op.kind, op.params
+            xs = self.shapes[op.inputs[0]]
+            if k == "eltwise":
+                self._c_eltwise(op)
+            elif k == "gemm":
+                self._c_gemm(op, oi)
+            elif k == "conv2d":
+                self._c_conv(op, oi)
+            elif k == "batched_gemm":
+                self._c_bgemm(op)
+            elif k == "attention":
+                self._c_attention(op)
+            elif k == "depthwise_conv":
+                n, h, w, c = xs
+                ho, wo = p["out_hw"]
+                R, S, _C = p["rsc"]
+                sh, sw = p["stride"]
+                pt, _pb, pl, _pr = p["pads"]
+                call("DEPTHWISE", io(op, 3),
+                     [n, h, w, c, R, S, sh, sw, pt, pl, ho, wo, _act(p)])
+            elif k in _ROWWISE:
+                call(_ROWWISE[k], io(op, 1), _rows_cols(xs))
+            elif k == "layernorm":
+                call("LAYERNORM", io(op, 3), _rows_cols(xs),
+                     [float(p["eps"])])
+            elif k == "bn_act":
+                c = xs[-1]
+                call("BN_ACT", io(op, 3),
+                     [int(np.prod(xs)) // c, c, _act(p)])
+            elif k == "global_mean":
+                n, h, w, c = xs
+                call("MEAN_MID", io(op, 1), [n, h * w, c])
+            elif k == "reduce_mean_mid":
+                d0, d1, d2 = xs
+                call("MEAN_MID", io(op, 1), [d0, d1, d2])
+            elif k == "pool":
+                n, h, w, c = xs
+                ho, wo = p["out_hw"]
+                kh, kw = p["ksize"]
+                sh, sw = p["stride"]
+                pt, pb, pl, pr = p["pads"]
+                call("POOL", io(op, 1),
+                     [1 if p["mode"] == "max" else 0,
+                      n, h, w, c, ho, wo, kh, kw, sh, sw, pt, pl])
+            elif k == "resize":
+                n, h, w, c = xs
+                ho, wo = p["out_hw"]
+                if (h, w) != tuple(p["in_hw"]) or \
+                        p["mode"] not in ("nearest", "bilinear"):
+                    raise RuntimeError(f"GPU resize: bad params {p}")
+                call("RESIZE", io(op, 1),
+                     [n, h, w, c, ho, wo,
+                      1 if p["mode"] == "bilinear" else 0,
+                      1 if p["align_corners"] else 0,
+                      1 if p["half_pixel_centers"] else 0])
+            elif k == "zero_insert":
+                n, h, w, c = xs
+                sh, sw = p["stride"]
+                if tuple(self.shapes[op.outputs[0]]) != \
+                        (n, (h - 1) * sh + 1, (w - 1) * sw + 1, c):
+                    raise RuntimeError(f"GPU zero_insert: bad params {p}")
+                call("ZERO_INSERT", io(op, 1), [n, h, w, c, sh, sw])
+            elif k == "transpose":
+                out_shape = self.shapes[op.outputs[0]]
+                in_strides = _strides(xs)
+                call("TRANSPOSE", io(op, 1),
+                     [len(out_shape)] + list(out_shape) +
+                     [in_strides[q] for q in p["perm"]] +
+                     [int(np.prod(out_shape))])
+            elif k == "gather":
+                ishape = self.shapes[op.inputs[1]]
+                call("GATHER", io(op, 2),
+                     [_numel(ishape), int(np.prod(xs[1:]))])
+            elif k == "strided_copy":
+                out_shape = self.shapes[op.outputs[0]]
+                istr = _strides(xs)
+                starts, steps = p["starts"], p["steps"]
+                shrink = p["shrink"]
+                offset = sum(starts[d] * istr[d] for d in range(len(xs)))
+                strides_out = [istr[d] * steps[d] for d in range(len(xs))
+                               if not shrink[d]]
+                src, dst = io(op, 1)
+                call("TRANSPOSE", [_off(src, offset * 2), dst],
+                     [max(len(out_shape), 1)] + (list(out_shape) or [1]) +
+                     (strides_out or [1]) + [_numel(out_shape)])
+            elif k == "cast":
+                call("CAST", io(op, 1),
+                     [_numel(xs), 0 if p["mode"] == "i2f" else 1])
+            elif k == "concat":
+                out_shape = self.shapes[op.outputs[0]]
+                axis = p["axis"]
+                ostr = _strides(out_shape)
+                off_elems = 0
+                for inp in op.inputs:
+                    ish = self.shapes[inp]
+                    call("SCATTER",
+                         [self._ptr(inp),
+                          _off(self._ptr(op.outputs[0]), off_elems * 2)],
+                         [len(ish)] + list(ish) + ostr + [_numel(ish)])
+                    off_elems += ish[axis] * ostr[axis]
+            elif k == "pad":
+                pads = p["pads"]
+                if len(xs) != 4 or any(p_[0] or p_[1]
+                                       for p_ in (pads[0], pads[3])):
+                    raise RuntimeError("GPU pad: only NHWC H/W pads")
+                call("PAD_NHWC", io(op, 1),
+                     list(xs) + [pads[1][0], pads[1][1], pads[2][0],
+                                 pads[2][1]])
+            else:
+                raise RuntimeError(f"GPU lowering: unsupported op {k}")
+
+    def _c_attention(self, op: PlanOp) -> None:
+        p = op.params
+        b_, s_, h_, d_ = self.shapes[op.inputs[0]]
+        ptrs = self._io(op, 3)
+        ints = [b_, s_, h_, d_]
+        if len(op.inputs) > 3:
+            # additive bias [b,h,q,S] (rank-4 padded), element strides
+            # with 0 = broadcast; checked against the resolved shape so
+            # a stride never walks past it
+            bshape = tuple(self.shapes[op.inputs[3]])
+            bshape = (1,) * (4 - len(bshape)) + bshape
+            batched, bh, bq = p["bias_dims"]
+            want = (b_ if batched else 1, bh, bq, s_)
+            if bshape != want or bh not in (1, h_) or bq not in (1, s_):
+                raise ValueError(
+                    f"attention bias shape {bshape} does not "
+                    f"match plan {want}")
+            ptrs.append(self._ptr(op.inputs[3]))
+            ints += [bh * bq * s_ if batched else 0,
+                     bq * s_ if bh == h_ else 0,
+                     s_ if bq == s_ else 0]
+        self._call("ATTENTION", ptrs, ints, [float(p["scale"])])
+
+    def _bcast_ints(self, out_shape, a_shape, b_shape):
+        nd = len(out_shape)
+        if nd > 6:
+            raise RuntimeError("eltwise rank > 6")
+
+        def strides_for(shape):
+            shape = list(shape)
+            shape = [1] * (nd - len(shape)) + shape
+            st = [0] * nd
+            acc = 1
+            for d in range(nd - 1, -1, -1):
+                if shape[d] == out_shape[d] and shape[d] != 1:
+                    st[d] = acc
+                elif shape[d] == 1 and out_shape[d] != 1:
+                    st[d] = 0
+                elif shape[d] == out_shape[d]:
+                    st[d] = acc   # both 1
+                else:
+                    raise RuntimeError(
+                        f"cannot broadcast {shape} to {out_shape}")
+                acc *= shape[d]
+            return st
+
+        return strides_for(a_shape), strides_for(b_shape)
+
+    def _c_eltwise(self, op: PlanOp) -> None:
+        fn = _ELT_CODE[op.params["fn"]]
+        out_shape = self.shapes[op.outputs[0]]
+        n_out = _numel(out_shape)
+        if len(op.inputs) == 1:
+            self._call("ELT_UNARY", self._io(op, 1), [n_out, fn])
+            return
+        a, b = op.inputs
+        sa_shape, sb_shape = self.shapes[a], self.shapes[b]
+        if tuple(sa_shape) == tuple(out_shape) == tuple(sb_shape):
+            ints = [n_out, fn, 1, n_out, 1, 1]
+        else:
+            sa, sb = self._bcast_ints(out_shape, sa_shape, sb_shape)
+            ints = [n_out, fn, len(out_shape)] + list(out_shape) + sa + sb
+        self._call("ELT_BINARY", self._io(op, 2), ints)
+
+    def _c_gemm(self, op: PlanOp, oi: int) -> None:
+        p = op.params
+        a_shape = self.shapes[op.inputs[0]]
+        M = int(np.prod(a_shape[:-1]))
+        K = a_shape[-1]
+        if p.get("trans_a"):
+            raise RuntimeError("gemm trans_a unsupported on GPU")
+        fp8 = self.dtype == "fp8"
+        wshape = self._weight_shape(op.inputs[1])
+        if wshape is None:
+            raise RuntimeError(
+                "fp8 gemm requires a constant weight" if fp8 else
+                "GPU gemm requires a constant weight operand; "
+                "activation x activation MatMul must be BatchMatMul")
+        # the kernels read the weight pre-transposed to [N][Kp] (the
+        # graph holds [K,N] unless trans_b), K zero-padded
+        N, Kw = wshape if p.get("trans_b") else wshape[::-1]
+        Kp = _pad128(Kw) if fp8 else _pad64(Kw)
+        wkey = (op.inputs[1], bool(p.get("trans_b")))
+        ni = 2
+        bias = res = None
+        if p.get("has_bias"):
+            bias = self._weight(op.inputs[ni])
+            ni += 1
+        if p.get("residual"):
+            res = self._ptr(op.inputs[ni])
+        a_ptr, out = self._io(op, 1)
+        ints = [M, N, Kp, _act(p)]
+        if fp8:
+            # fp8 serving path: rowwise-quantize the activation into
+            # scratch, then the e4m3 MFMA GEMM with per-row x per-col
+            # dequant in the epilogue (engine.dtype: fp8)
+            q_ptr = self._scratch(oi)
+            sa_ptr = _off(q_ptr, _pad256b(M * Kp))
+            self._call("QUANT_FP8", [a_ptr, q_ptr, sa_ptr], [M, K, Kp])
+            self._call("GEMM_FP8",
+                       [q_ptr, sa_ptr, (("f8q",) + wkey, 0),
+                        (("f8s",) + wkey, 0), bias, res, out], ints)
+            return
+        if Kp != K:
+            # zero-pad the activation's K to the weight's 64-aligned Kp
+            scratch = self._scratch(oi)
+            self._call("PAD_LAST", [a_ptr, scratch], [M, K, Kp])
+            a_ptr = scratch
+        self._call("GEMM", [a_ptr, (("gw",) + wkey, 0), bias, res, out],
+                   ints, [1.0])
+
+    def _c_conv(self, op: PlanOp, oi: int) -> None:
+        p = op.params
+        R, S, Cin, Kc = p["rsck"]
+        sh, sw = p["stride"]
+        pt, pb, pl, pr = p["pads"]
+        Ho, Wo = p["out_hw"]
+        x = op.inputs[0]
+        w_idx = op.inputs[1]
+        n, H, W, C = self.shapes[x]
+        M = n * Ho * Wo
+        bias = self._weight(op.inputs[2])
+        res = self._ptr(op.inputs[3]) if p.get("residual") else None
+        wshape = self._weight_shape(w_idx)            # [R,S,C,K] master
+        if wshape is None:
+            raise KeyError(f"no master weight for tensor {w_idx}")
+        wR, wS, wC, _wK = wshape
+        act = _act(p)
+        out = self._ptr(op.outputs[0])
+        zeros = (("zeros",), 0)
+        if R == 1 and S == 1 and (sh, sw) == (1, 1) and \
+                (pt, pb, pl, pr) == (0, 0, 0, 0) and C % 64 == 0:
+            self._call("GEMM",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res, out],
+                       [M, Kc, C, act], [1.0])
+        elif C % 8 == 0:
+            # fused implicit-GEMM (no im2col materialization)
+            self._call("CONV",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res,
+                        zeros, out],
+                       [n, H, W, C, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                        _pad64(wR * wS * wC), act])
+        else:
+            # C % 8 != 0 (RGB stem): widen channels to C8 with zeros,
+            # then the fused conv with channel-padded weights
+            c8 = (C + 7) // 8 * 8
+            scratch = self._scratch(oi)
+            self._call("PAD_LAST", [self._ptr(x), scratch],
+                       [n * H * W, C, c8])
+            self._call("CONV",
+                       [scratch, (("cw", w_idx, "cpad", c8), 0), bias,
+                        res, zeros, out],
+                       [n, H, W, c8, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                        _pad64(wR * wS * c8), act])
+
+    def _c_bgemm(self, op: PlanOp) -> None:
+        p = op.params
+        a_shape = self.shapes[op.inputs[0]]
+        b_shape = self.shapes[op.inputs[1]]
+        if p.get("trans_a"):
+            raise RuntimeError("batched_gemm trans_a unsupported")
+        trans_b = bool(p.get("trans_b"))
+        M, K = a_shape[-2], a_shape[-1]
+        N = b_shape[-2] if trans_b else b_shape[-1]
+        bat_a = int(np.prod(a_shape[:-2])) if len(a_shape) > 2 else 1
+        bat_b = int(np.prod(b_shape[:-2])) if len(b_shape) > 2 else 1
+        sA = M * K if bat_a > 1 else 0
+        sB = (b_shape[-1] * b_shape[-2]) if bat_b > 1 else 0
+        self._call("BGEMM", self._io(op, 2),
+                   [max(bat_a, bat_b), M, N, K, sA, sB, M * N,
+                    1 if trans_b else 0], [1.0])

@@ -1,12 +1,18 @@
-"""GPU lowering: Plan -> CDNA4 kernel-call sequences.
+"""GPU residency: a Plan's weights and execution contexts on one device.
 
-Responsibilities (all ahead of the hot path):
-  * weight layout transforms at model-load time — GEMM/conv weights are
-    pre-transposed to [N][K] bf16 with K zero-padded to a multiple of 64
-    so both MFMA fragments read contiguously along K (see csrc/ops/gemm.hip);
-  * per-batch-bucket ExecContexts: shapes resolved, every activation
-    assigned an offset in one workspace arena (liveness-based reuse),
-    kernel calls emitted with raw pointers; optionally hipGraph-captured;
+What kernels a plan runs, on which buffers, is decided without a GPU in
+engine/emit.py: a call template per (plan, batch bucket, dtype) whose
+pointers are (region key, offset) descriptors. This module gives the
+template memory (all ahead of the hot path):
+  * weights: one bf16 master blob in the layout emit.blob_layout fixes,
+    plus layout transforms keyed as the template names them — GEMM/conv
+    weights pre-transposed to [N][K] bf16 with K zero-padded to a
+    multiple of 64 so both MFMA fragments read contiguously along K
+    (see csrc/ops/gemm.hip), fp8 GEMM weights with row scales — computed
+    on first use or restored from the plan's pinned transform arena;
+  * per-batch-bucket ExecContexts: a workspace arena, the template's
+    region keys resolved to base addresses, the calls rebased by
+    ext.instantiate_plan; optionally hipGraph-captured;
   * the per-request path is: H2D feed copies -> ExecPlan.run ->
     D2H fetches. Weights stay resident (the HBM3E model pool).
 
@@ -19,14 +25,15 @@ from __future__ import annotations
 import contextlib
 import logging
 import threading
-from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import warnings
 
 import numpy as np
 
-from .planner import Plan, PlanOp, is_sym, resolve_dim
+from .emit import (WS, _pad64, _pad128, _pad256b, blob_layout,
+                   build_template)
+from .planner import Plan, is_sym, resolve_dim
 
 # weight arrays from memory-mapped SavedModels are read-only; we only
 # ever READ the torch views of them (H2D staging), so the non-writable
@@ -76,8 +83,6 @@ def gpu_available() -> bool:
     except Exception:       # noqa: BLE001
         return False
 
-
-ALIGN = 256  # byte alignment of workspace slices
 
 # shared pinned staging for weight uploads (64 MiB bf16), reused across
 # model loads under a lock — page-locking memory per load is slower than
@@ -290,37 +295,6 @@ def _get_upload_stream(torch, device: str):
         return s
 
 
-def _pad64(k: int) -> int:
-    return (k + 63) // 64 * 64
-
-
-def _pad128(k: int) -> int:
-    return (k + 127) // 128 * 128
-
-
-def _pad256b(n: int) -> int:
-    return (n + 255) // 256 * 256
-
-
-_ACT_CODE = {"none": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "gelu": 4,
-             "relu6": 5}
-
-_ELT_CODE = {
-    "add": 0, "sub": 1, "mul": 2, "div": 3, "max": 4, "min": 5,
-    "sqdiff": 6, "relu": 7, "tanh": 8, "sigmoid": 9, "erf": 10,
-    "sqrt": 11, "rsqrt": 12, "exp": 13, "neg": 14, "square": 15,
-    "gelu": 16, "relu6": 17,
-}
-
-
-@dataclass
-class _BufInfo:
-    offset: int = -1          # byte offset in workspace
-    nbytes: int = 0
-    shape: Tuple[int, ...] = ()
-    is_int: bool = False
-
-
 # ---------------------------------------------------------------------------
 # plan-level context templates + transform arenas.
 #
@@ -330,10 +304,10 @@ class _BufInfo:
 # transforms, and under GIL contention with the serving threads that
 # Python work WAS the cold-load cost. Both are plan-deterministic:
 #
-#  * the CONTEXT TEMPLATE caches shapes/roots/buffer offsets/scratch
-#    and the emitted kernel calls with every pointer classified as
-#    (region key, offset); a new context for any model sharing the plan
-#    instantiates by pure pointer relocation;
+#  * the CONTEXT TEMPLATE (engine/emit.py) holds shapes/roots/buffer
+#    offsets/scratch and the kernel calls with every pointer written as
+#    (region key, offset); every context is instantiated from it by
+#    pure pointer relocation, and models sharing the plan share it;
 #  * the TRANSFORM ARENA caches the transformed weight bytes
 #    (pre-transposed GEMM/conv layouts, fp8 quantized weights) in
 #    pinned host memory; a new model restores them with ONE DMA into a
@@ -345,8 +319,9 @@ _TMPL_CAP = 64          # templates are ~100 KB of host data each
 _ARENA_CAP = 4          # arenas pin ~50 MB of host RAM each (like the
                         # blob cache: only the hottest plan contents)
 _tmpl_lock = threading.Lock()
-_ctx_templates: Dict[tuple, object] = {}    # (id(plan),bucket,dtype) ->
-                                            # (plan, template|None)
+_ctx_templates: Dict[tuple, tuple] = {}     # (id(plan),bucket,dtype) ->
+                                            # (plan, (Template,
+                                            #         ext.CallTemplate))
 _tmpl_order: List[tuple] = []
 _transform_arenas: Dict[tuple, tuple] = {}  # (id(plan),dtype) ->
                                             # (plan, entries, pinned)
@@ -398,6 +373,19 @@ def _put_transform_arena(plan, dtype: str, entries, pinned) -> None:
             _transform_arenas.pop(old, None)
 
 
+def _call_template(ext, tmpl):
+    """The C++ form of a template's calls: kinds by the extension's
+    K_* value, pointers as (0, off) workspace | (1, region index, off)
+    | (2,) null."""
+    index = {k: i for i, k in enumerate(tmpl.region_keys)}
+    return ext.CallTemplate([
+        (getattr(ext, "K_" + kind),
+         [(2,) if d is None else (0, d[1]) if d[0] == WS
+          else (1, index[d[0]], d[1]) for d in descs],
+         ints, floats)
+        for kind, descs, ints, floats in tmpl.calls])
+
+
 class ExecContext:
     """Shapes + workspace + calls for one batch bucket."""
 
@@ -408,52 +396,37 @@ class ExecContext:
         plan = gm.plan
         dev = gm.device
 
-        tmpl = _get_ctx_template(plan, batch, gm.dtype)
-        done = False
-        if tmpl:
-            # relocation fast path: all the Python-heavy planning and
-            # emission was done once for this (plan, bucket); allocate
-            # the workspace and instantiate the C++ call template with
-            # rebased pointers (one pybind call)
-            self.shapes = tmpl["shapes"]
-            self.root = tmpl["root"]
-            self.bufs = tmpl["bufs"]
-            self.total_bytes = tmpl["total_bytes"]
-            self.scratch_off = tmpl["scratch_off"]
-            self.workspace = torch.empty(self.total_bytes,
-                                         dtype=torch.uint8, device=dev)
-            try:
-                bases = gm.region_bases()
-                base_list = [bases[k] for k in tmpl["region_keys"]]
-                self.exec_plan = ext.instantiate_plan(
-                    tmpl["ctmpl"], self.workspace.data_ptr(), base_list)
-                done = True
-                self._from_template = True
-            except KeyError:
-                # this model is missing a region (e.g. the transform
-                # arena failed to publish) — fall through to full emit
-                done = False
-        if not done:
-            self.shapes: List[Tuple[int, ...]] = [
-                plan.resolve_shape(t.shape, batch) for t in plan.tensors]
-            self.root = [t.alias_of if t.alias_of is not None else t.idx
-                         for t in plan.tensors]
-            # resolve alias chains
-            for i, r in enumerate(self.root):
-                seen = 0
-                while plan.tensors[r].alias_of is not None and seen < 16:
-                    r = plan.tensors[r].alias_of
-                    seen += 1
-                self.root[i] = r
-
-            self._plan_buffers()
-            self.workspace = torch.empty(self.total_bytes,
-                                         dtype=torch.uint8, device=dev)
-            calls = self._emit_calls()
-            if tmpl is None:            # not attempted yet (None = new)
-                self._register_template(calls)
-            self.exec_plan = ext.ExecPlan(calls)
-            self._from_template = False
+        # all the Python-heavy planning and emission is done once per
+        # (plan, bucket, dtype); a context is the template plus device
+        # memory: allocate the workspace, resolve the template's weight
+        # regions to base addresses and rebase the calls (one pybind
+        # call)
+        cached = _get_ctx_template(plan, batch, gm.dtype)
+        if cached is None:
+            tmpl = build_template(plan, batch, gm.dtype)
+            ctmpl = _call_template(ext, tmpl)
+        else:
+            tmpl, ctmpl = cached
+        self.shapes = tmpl.shapes
+        self.root = tmpl.root
+        self.bufs = tmpl.bufs
+        self.total_bytes = tmpl.total_bytes
+        self.scratch_off = tmpl.scratch_off
+        self.workspace = torch.empty(self.total_bytes,
+                                     dtype=torch.uint8, device=dev)
+        n_before = gm.n_transforms()
+        bases = gm.region_bases(tmpl.region_keys)
+        self.exec_plan = ext.instantiate_plan(
+            ctmpl, self.workspace.data_ptr(), bases)
+        # a context whose template was cached and whose transforms all
+        # existed needs no eager warm-up run before capture (prewarm)
+        self._from_template = cached is not None and \
+            gm.n_transforms() == n_before
+        if cached is None:
+            _put_ctx_template(plan, batch, gm.dtype, (tmpl, ctmpl))
+            # the template's region keys must be resolvable by later
+            # models sharing the plan — snapshot the transform bytes now
+            gm.publish_transform_arena()
         self.captured = False
         self._views: Dict[int, object] = {}
         self.lock = threading.Lock()
@@ -470,8 +443,8 @@ class ExecContext:
 
     def capture_only(self):
         """Capture the hipGraph WITHOUT an eager warm-up run: valid
-        for template-instantiated contexts, where every buffer and
-        transform already exists (the warm-up run existed to flush
+        for contexts whose template was cached and whose transforms
+        all existed (_from_template; the warm-up run existed to flush
         lazy allocations before capture). Saves a full model execution
         per cold load under LRU churn."""
         torch, _ = _load_backend()
@@ -483,577 +456,6 @@ class ExecContext:
             except Exception:       # noqa: BLE001
                 log.exception("hipGraph capture failed; staying eager")
             self.captured = True
-
-    def _register_template(self, calls) -> None:
-        """Classify every emitted pointer into (workspace | weight
-        region | null) and cache the relocatable template for this
-        (plan, bucket, dtype). If any pointer can't be classified the
-        template is disabled for this key (correctness first)."""
-        torch, ext = _load_backend()
-        gm = self.gm
-        ws_base = self.workspace.data_ptr()
-        ws_end = ws_base + self.total_bytes
-        regions = gm.region_list()       # [(base, size, key)] sorted
-        region_keys: List = []
-        key_index: Dict = {}
-        tcalls = []
-        try:
-            for kind, ptrs, ints, floats in calls:
-                descs = []
-                for p in ptrs:
-                    if p == 0:
-                        descs.append((2,))
-                    elif ws_base <= p < ws_end:
-                        descs.append((0, p - ws_base))
-                    else:
-                        hit = None
-                        for base, size, key in regions:
-                            if base <= p < base + size:
-                                if key not in key_index:
-                                    key_index[key] = len(region_keys)
-                                    region_keys.append(key)
-                                hit = (1, key_index[key], p - base)
-                                break
-                        if hit is None:
-                            raise KeyError(f"unclassifiable ptr {p:#x}")
-                        descs.append(hit)
-                tcalls.append((kind, descs, list(ints), list(floats)))
-        except KeyError as e:
-            log.warning("context template disabled for bucket %d: %s",
-                        self.batch, e)
-            _put_ctx_template(gm.plan, self.batch, gm.dtype, False)
-            return
-        tmpl = {"shapes": self.shapes, "root": self.root,
-                "bufs": self.bufs, "total_bytes": self.total_bytes,
-                "scratch_off": self.scratch_off,
-                "region_keys": region_keys,
-                "ctmpl": ext.CallTemplate(tcalls)}
-        _put_ctx_template(gm.plan, self.batch, gm.dtype, tmpl)
-        # the template's region keys must be resolvable by later models
-        # sharing the plan — snapshot the transform bytes now
-        gm.publish_transform_arena()
-
-    # -- buffer planning ---------------------------------------------------
-    def _buf_bytes(self, idx: int) -> int:
-        t = self.gm.plan.tensors[idx]
-        n = int(np.prod(self.shapes[idx])) if self.shapes[idx] else 1
-        esize = 4 if t.dtype == "i32" else 2
-        return max(n * esize, esize)
-
-    def _plan_buffers(self) -> None:
-        plan = self.gm.plan
-        live_end: Dict[int, int] = {}
-        scratch_sizes: Dict[int, int] = {}   # op_idx -> scratch bytes
-
-        def root(i):
-            return self.root[i]
-
-        n_ops = len(plan.ops)
-        for oi, op in enumerate(plan.ops):
-            for i in op.inputs + op.outputs:
-                live_end[root(i)] = oi
-        for i in plan.sig_outputs.values():
-            live_end[root(i)] = n_ops + 1
-        for alias, i in plan.sig_inputs.items():
-            live_end.setdefault(root(i), -1)
-            live_end[root(i)] = max(live_end[root(i)], 0)
-
-        # scratch sizes (conv channel-pad, gemm K-pad)
-        for oi, op in enumerate(plan.ops):
-            if op.kind == "gemm":
-                a_shape = self.shapes[op.inputs[0]]
-                K = a_shape[-1]
-                M = int(np.prod(a_shape[:-1]))
-                if self.gm.dtype == "fp8":
-                    # quantized activations (u8 [M, Kp128]) + row scales
-                    Kp = _pad128(K)
-                    scratch_sizes[oi] = _pad256b(M * Kp) + M * 4
-                elif K % 64 != 0:
-                    scratch_sizes[oi] = M * _pad64(K) * 2
-            if op.kind == "conv2d":
-                R, S, Cin, Kc = op.params["rsck"]
-                is_1x1 = (R == 1 and S == 1 and
-                          op.params["stride"] == (1, 1) and
-                          op.params["pads"] == (0, 0, 0, 0) and
-                          Cin % 64 == 0)
-                # channel-pad scratch for the C%8!=0 case (RGB stem):
-                # input widened to C8 channels, then fused conv
-                if not is_1x1 and Cin % 8 != 0:
-                    H, W = op.params["hw"]
-                    c8 = (Cin + 7) // 8 * 8
-                    scratch_sizes[oi] = self.batch * H * W * c8 * 2
-
-        self.bufs: Dict[int, _BufInfo] = {}
-        self.scratch_off: Dict[int, int] = {}
-        free: List[Tuple[int, int]] = []     # (nbytes, offset)
-        cursor = 0
-
-        def alloc(nbytes: int) -> int:
-            nonlocal cursor
-            nbytes = (nbytes + ALIGN - 1) // ALIGN * ALIGN
-            best = None
-            for j, (sz, off) in enumerate(free):
-                if sz >= nbytes and (best is None or sz < free[best][0]):
-                    best = j
-            if best is not None:
-                sz, off = free.pop(best)
-                if sz > nbytes:
-                    free.append((sz - nbytes, off + nbytes))
-                return off
-            off = cursor
-            cursor += nbytes
-            return off
-
-        def release(off: int, nbytes: int) -> None:
-            nbytes = (nbytes + ALIGN - 1) // ALIGN * ALIGN
-            free.append((nbytes, off))
-
-        def ensure(idx: int) -> None:
-            r = root(idx)
-            if r in self.bufs:
-                return
-            nb = self._buf_bytes(r)
-            self.bufs[r] = _BufInfo(alloc(nb), nb, self.shapes[r],
-                                    plan.tensors[r].dtype == "i32")
-
-        # inputs first (persistent through the run)
-        for i in plan.sig_inputs.values():
-            ensure(i)
-        for oi, op in enumerate(plan.ops):
-            for i in op.outputs:
-                ensure(i)
-            if oi in scratch_sizes:
-                self.scratch_off[oi] = alloc(scratch_sizes[oi])
-                release(self.scratch_off[oi], scratch_sizes[oi])
-                # NOTE: scratch freed immediately after alloc so the NEXT
-                # op's outputs can reuse it; but it must survive through
-                # this op — handled because outputs were allocated first.
-            for i in op.inputs:
-                r = root(i)
-                if r in self.bufs and live_end.get(r, -1) == oi and \
-                        plan.tensors[r].kind != "input" and \
-                        live_end[r] <= n_ops:
-                    release(self.bufs[r].offset, self.bufs[r].nbytes)
-        self.total_bytes = max(cursor, ALIGN)
-
-    # -- call emission -----------------------------------------------------
-    def _ptr(self, idx: int) -> int:
-        r = self.root[idx]
-        t = self.gm.plan.tensors[r]
-        if t.kind == "weight":
-            return self.gm.weight_ptr(r)
-        return self.workspace.data_ptr() + self.bufs[r].offset
-
-    def _emit_calls(self) -> list:
-        torch, ext = _load_backend()
-        plan = self.gm.plan
-        calls = []
-        for oi, op in enumerate(plan.ops):
-            k = op.kind
-            p = op.params
-            if k == "eltwise":
-                calls.extend(self._c_eltwise(op, ext))
-            elif k == "gemm":
-                calls.extend(self._c_gemm(op, oi, ext))
-            elif k == "conv2d":
-                calls.extend(self._c_conv(op, oi, ext))
-            elif k == "depthwise_conv":
-                n, h, w_, c = self.shapes[op.inputs[0]]
-                ho, wo = p["out_hw"]
-                R, S, _C = p["rsc"]
-                sh, sw = p["stride"]
-                pt, _pb, pl, _pr = p["pads"]
-                calls.append((ext.K_DEPTHWISE,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.inputs[1]),
-                               self._ptr(op.inputs[2]),
-                               self._ptr(op.outputs[0])],
-                              [n, h, w_, c, R, S, sh, sw, pt, pl,
-                               ho, wo, _ACT_CODE[p.get("act", "none")]],
-                              []))
-            elif k == "batched_gemm":
-                calls.extend(self._c_bgemm(op, ext))
-            elif k == "attention":
-                b_, s_, h_, d_ = self.shapes[op.inputs[0]]
-                ptrs = [self._ptr(op.inputs[0]),
-                        self._ptr(op.inputs[1]),
-                        self._ptr(op.inputs[2]),
-                        self._ptr(op.outputs[0])]
-                ints = [b_, s_, h_, d_]
-                if len(op.inputs) > 3:
-                    # additive bias [b,h,q,S] (rank-4 padded), element
-                    # strides with 0 = broadcast; checked against the
-                    # resolved shape so a stride never walks past it
-                    bshape = tuple(self.shapes[op.inputs[3]])
-                    bshape = (1,) * (4 - len(bshape)) + bshape
-                    batched, bh, bq = p["bias_dims"]
-                    want = (b_ if batched else 1, bh, bq, s_)
-                    if bshape != want or bh not in (1, h_) or \
-                            bq not in (1, s_):
-                        raise ValueError(
-                            f"attention bias shape {bshape} does not "
-                            f"match plan {want}")
-                    ptrs.append(self._ptr(op.inputs[3]))
-                    ints += [bh * bq * s_ if batched else 0,
-                             bq * s_ if bh == h_ else 0,
-                             s_ if bq == s_ else 0]
-                calls.append((ext.K_ATTENTION, ptrs, ints,
-                              [float(p["scale"])]))
-            elif k == "softmax":
-                shape = self.shapes[op.inputs[0]]
-                rows = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
-                calls.append((ext.K_SOFTMAX,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [rows, shape[-1]], []))
-            elif k == "layernorm":
-                shape = self.shapes[op.inputs[0]]
-                rows = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
-                calls.append((ext.K_LAYERNORM,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.inputs[1]),
-                               self._ptr(op.inputs[2]),
-                               self._ptr(op.outputs[0])],
-                              [rows, shape[-1]], [float(p["eps"])]))
-            elif k == "bn_act":
-                shape = self.shapes[op.inputs[0]]
-                c = shape[-1]
-                rows = int(np.prod(shape)) // c
-                calls.append((ext.K_BN_ACT,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.inputs[1]),
-                               self._ptr(op.inputs[2]),
-                               self._ptr(op.outputs[0])],
-                              [rows, c, _ACT_CODE[p.get("act", "none")]],
-                              []))
-            elif k == "global_mean":
-                n, h, w, c = self.shapes[op.inputs[0]]
-                calls.append((ext.K_MEAN_MID,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [n, h * w, c], []))
-            elif k == "reduce_mean_mid":
-                d0, d1, d2 = self.shapes[op.inputs[0]]
-                calls.append((ext.K_MEAN_MID,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [d0, d1, d2], []))
-            elif k == "reduce_mean_last":
-                shape = self.shapes[op.inputs[0]]
-                rows = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
-                calls.append((ext.K_MEAN_LAST,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [rows, shape[-1]], []))
-            elif k == "pool":
-                n, h, w, c = self.shapes[op.inputs[0]]
-                ho, wo = p["out_hw"]
-                kh, kw = p["ksize"]
-                sh, sw = p["stride"]
-                pt, pb, pl, pr = p["pads"]
-                calls.append((ext.K_POOL,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [1 if p["mode"] == "max" else 0,
-                               n, h, w, c, ho, wo, kh, kw, sh, sw, pt, pl],
-                              []))
-            elif k == "resize":
-                n, h, w, c = self.shapes[op.inputs[0]]
-                ho, wo = p["out_hw"]
-                if (h, w) != tuple(p["in_hw"]) or \
-                        p["mode"] not in ("nearest", "bilinear"):
-                    raise RuntimeError(f"GPU resize: bad params {p}")
-                calls.append((ext.K_RESIZE,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [n, h, w, c, ho, wo,
-                               1 if p["mode"] == "bilinear" else 0,
-                               1 if p["align_corners"] else 0,
-                               1 if p["half_pixel_centers"] else 0],
-                              []))
-            elif k == "zero_insert":
-                n, h, w, c = self.shapes[op.inputs[0]]
-                sh, sw = p["stride"]
-                if tuple(self.shapes[op.outputs[0]]) != \
-                        (n, (h - 1) * sh + 1, (w - 1) * sw + 1, c):
-                    raise RuntimeError(f"GPU zero_insert: bad params {p}")
-                calls.append((ext.K_ZERO_INSERT,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [n, h, w, c, sh, sw], []))
-            elif k == "transpose":
-                in_shape = self.shapes[op.inputs[0]]
-                perm = p["perm"]
-                out_shape = self.shapes[op.outputs[0]]
-                in_strides = [1] * len(in_shape)
-                for d in range(len(in_shape) - 2, -1, -1):
-                    in_strides[d] = in_strides[d + 1] * in_shape[d + 1]
-                strides_out = [in_strides[q] for q in perm]
-                n_out = int(np.prod(out_shape))
-                calls.append((ext.K_TRANSPOSE,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [len(out_shape)] + list(out_shape) +
-                              strides_out + [n_out], []))
-            elif k == "gather":
-                tshape = self.shapes[op.inputs[0]]
-                ishape = self.shapes[op.inputs[1]]
-                row = int(np.prod(tshape[1:]))
-                n_idx = int(np.prod(ishape)) if ishape else 1
-                calls.append((ext.K_GATHER,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.inputs[1]),
-                               self._ptr(op.outputs[0])],
-                              [n_idx, row], []))
-            elif k == "strided_copy":
-                in_shape = self.shapes[op.inputs[0]]
-                out_shape = self.shapes[op.outputs[0]]
-                istr = [1] * len(in_shape)
-                for d in range(len(in_shape) - 2, -1, -1):
-                    istr[d] = istr[d + 1] * in_shape[d + 1]
-                starts, steps = p["starts"], p["steps"]
-                shrink = p["shrink"]
-                offset = sum(starts[d] * istr[d]
-                             for d in range(len(in_shape)))
-                strides_out = [istr[d] * steps[d]
-                               for d in range(len(in_shape))
-                               if not shrink[d]]
-                n_out = int(np.prod(out_shape)) if out_shape else 1
-                nd_out = max(len(out_shape), 1)
-                od = list(out_shape) or [1]
-                so = strides_out or [1]
-                calls.append((ext.K_TRANSPOSE,
-                              [self._ptr(op.inputs[0]) + offset * 2,
-                               self._ptr(op.outputs[0])],
-                              [nd_out] + od + so + [n_out], []))
-            elif k == "cast":
-                shape = self.shapes[op.inputs[0]]
-                n = int(np.prod(shape)) if shape else 1
-                calls.append((ext.K_CAST,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [n, 0 if p["mode"] == "i2f" else 1], []))
-            elif k == "argmax_last":
-                shape = self.shapes[op.inputs[0]]
-                rows = int(np.prod(shape[:-1])) if len(shape) > 1 else 1
-                calls.append((ext.K_ARGMAX_LAST,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [rows, shape[-1]], []))
-            elif k == "concat":
-                out_shape = self.shapes[op.outputs[0]]
-                axis = p["axis"]
-                ostr = [1] * len(out_shape)
-                for d in range(len(out_shape) - 2, -1, -1):
-                    ostr[d] = ostr[d + 1] * out_shape[d + 1]
-                off_elems = 0
-                for inp in op.inputs:
-                    ish = self.shapes[inp]
-                    n_in = int(np.prod(ish)) if ish else 1
-                    calls.append((ext.K_SCATTER,
-                                  [self._ptr(inp),
-                                   self._ptr(op.outputs[0]) +
-                                   off_elems * 2],
-                                  [len(ish)] + list(ish) + ostr +
-                                  [n_in], []))
-                    off_elems += ish[axis] * ostr[axis]
-            elif k == "pad":
-                shape = self.shapes[op.inputs[0]]
-                pads = p["pads"]
-                if len(shape) != 4 or any(p_[0] or p_[1]
-                                          for p_ in (pads[0], pads[3])):
-                    raise RuntimeError("GPU pad: only NHWC H/W pads")
-                calls.append((ext.K_PAD_NHWC,
-                              [self._ptr(op.inputs[0]),
-                               self._ptr(op.outputs[0])],
-                              [shape[0], shape[1], shape[2], shape[3],
-                               pads[1][0], pads[1][1], pads[2][0],
-                               pads[2][1]], []))
-            else:
-                raise RuntimeError(f"GPU lowering: unsupported op {k}")
-        return calls
-
-    def _bcast_ints(self, out_shape, a_shape, b_shape):
-        nd = len(out_shape)
-        if nd > 6:
-            raise RuntimeError("eltwise rank > 6")
-
-        def strides_for(shape):
-            shape = list(shape)
-            shape = [1] * (nd - len(shape)) + shape
-            st = [0] * nd
-            acc = 1
-            for d in range(nd - 1, -1, -1):
-                if shape[d] == out_shape[d] and shape[d] != 1:
-                    st[d] = acc
-                elif shape[d] == 1 and out_shape[d] != 1:
-                    st[d] = 0
-                elif shape[d] == out_shape[d]:
-                    st[d] = acc   # both 1
-                else:
-                    raise RuntimeError(
-                        f"cannot broadcast {shape} to {out_shape}")
-                acc *= shape[d]
-            return st
-
-        return strides_for(a_shape), strides_for(b_shape)
-
-    def _c_eltwise(self, op: PlanOp, ext):
-        fn = _ELT_CODE[op.params["fn"]]
-        out = op.outputs[0]
-        out_shape = self.shapes[out]
-        n_out = int(np.prod(out_shape)) if out_shape else 1
-        if len(op.inputs) == 1:
-            return [(ext.K_ELT_UNARY,
-                     [self._ptr(op.inputs[0]), self._ptr(out)],
-                     [n_out, fn], [])]
-        a, b = op.inputs
-        sa_shape, sb_shape = self.shapes[a], self.shapes[b]
-        if tuple(sa_shape) == tuple(out_shape) == tuple(sb_shape):
-            return [(ext.K_ELT_BINARY,
-                     [self._ptr(a), self._ptr(b), self._ptr(out)],
-                     [n_out, fn, 1, n_out, 1, 1], [])]
-        sa, sb = self._bcast_ints(out_shape, sa_shape, sb_shape)
-        nd = len(out_shape)
-        ints = [n_out, fn, nd] + list(out_shape) + sa + sb
-        return [(ext.K_ELT_BINARY,
-                 [self._ptr(a), self._ptr(b), self._ptr(out)], ints, [])]
-
-    def _c_gemm(self, op: PlanOp, oi: int, ext):
-        p = op.params
-        a = op.inputs[0]
-        w_plan_idx = op.inputs[1]
-        a_shape = self.shapes[a]
-        M = int(np.prod(a_shape[:-1]))
-        K = a_shape[-1]
-        if p.get("trans_a"):
-            raise RuntimeError("gemm trans_a unsupported on GPU")
-        if self.gm.dtype == "fp8":
-            return self._c_gemm_fp8(op, oi, ext)
-        wt = self.gm.gemm_weight(w_plan_idx, bool(p.get("trans_b")))
-        N = wt.shape[0]
-        Kp = wt.shape[1]
-        ni = 2
-        bias_ptr = 0
-        res_ptr = 0
-        if p.get("has_bias"):
-            bias_ptr = self.gm.weight_ptr(op.inputs[ni])
-            ni += 1
-        if p.get("residual"):
-            res_ptr = self._ptr(op.inputs[ni])
-        calls = []
-        a_ptr = self._ptr(a)
-        if Kp != K:
-            # zero-pad the activation's K to the weight's 64-aligned Kp
-            scratch = self.workspace.data_ptr() + self.scratch_off[oi]
-            calls.append((ext.K_PAD_LAST, [a_ptr, scratch], [M, K, Kp], []))
-            a_ptr = scratch
-        calls.append((ext.K_GEMM,
-                      [a_ptr, wt.data_ptr(), bias_ptr, res_ptr,
-                       self._ptr(op.outputs[0])],
-                      [M, N, Kp, _ACT_CODE[p.get("act", "none")]],
-                      [1.0]))
-        return calls
-
-    def _c_gemm_fp8(self, op: PlanOp, oi: int, ext):
-        """fp8 serving path: rowwise-quantize the activation into
-        scratch, then the e4m3 MFMA GEMM with per-row x per-col dequant
-        in the epilogue (engine.dtype: fp8)."""
-        p = op.params
-        a = op.inputs[0]
-        w_plan_idx = op.inputs[1]
-        a_shape = self.shapes[a]
-        M = int(np.prod(a_shape[:-1]))
-        K = a_shape[-1]
-        wq, wscale = self.gm.gemm_weight_fp8(w_plan_idx,
-                                             bool(p.get("trans_b")))
-        N, Kp = wq.shape
-        ni = 2
-        bias_ptr = 0
-        res_ptr = 0
-        if p.get("has_bias"):
-            bias_ptr = self.gm.weight_ptr(op.inputs[ni])
-            ni += 1
-        if p.get("residual"):
-            res_ptr = self._ptr(op.inputs[ni])
-        scratch = self.workspace.data_ptr() + self.scratch_off[oi]
-        q_ptr = scratch
-        sa_ptr = scratch + _pad256b(M * Kp)
-        return [
-            (ext.K_QUANT_FP8, [self._ptr(a), q_ptr, sa_ptr],
-             [M, K, Kp], []),
-            (ext.K_GEMM_FP8,
-             [q_ptr, sa_ptr, wq.data_ptr(), wscale.data_ptr(),
-              bias_ptr, res_ptr, self._ptr(op.outputs[0])],
-             [M, N, Kp, _ACT_CODE[p.get("act", "none")]], []),
-        ]
-
-    def _c_conv(self, op: PlanOp, oi: int, ext):
-        p = op.params
-        R, S, Cin, Kc = p["rsck"]
-        sh, sw = p["stride"]
-        pt, pb, pl, pr = p["pads"]
-        Ho, Wo = p["out_hw"]
-        x = op.inputs[0]
-        n, H, W, C = self.shapes[x]
-        M = n * Ho * Wo
-        bias_ptr = self.gm.weight_ptr(op.inputs[2])
-        res_ptr = self._ptr(op.inputs[3]) if p.get("residual") else 0
-        wt = self.gm.conv_weight(op.inputs[1])
-        Kp = wt.shape[1]
-        act = _ACT_CODE[p.get("act", "none")]
-        if R == 1 and S == 1 and (sh, sw) == (1, 1) and \
-                (pt, pb, pl, pr) == (0, 0, 0, 0) and C % 64 == 0:
-            return [(ext.K_GEMM,
-                     [self._ptr(x), wt.data_ptr(), bias_ptr, res_ptr,
-                      self._ptr(op.outputs[0])],
-                     [M, Kc, C, act], [1.0])]
-        if C % 8 == 0:
-            # fused implicit-GEMM (no im2col materialization)
-            return [(ext.K_CONV,
-                     [self._ptr(x), wt.data_ptr(), bias_ptr, res_ptr,
-                      self.gm.zeros_ptr(), self._ptr(op.outputs[0])],
-                     [n, H, W, C, Kc, R, S, sh, sw, pt, pl, Ho, Wo, Kp,
-                      act], [])]
-        # C % 8 != 0 (RGB stem): widen channels to C8 with zeros, then the
-        # fused conv with channel-padded weights
-        c8 = (C + 7) // 8 * 8
-        wt8 = self.gm.conv_weight_cpad(op.inputs[1], c8)
-        Kp8 = wt8.shape[1]
-        scratch = self.workspace.data_ptr() + self.scratch_off[oi]
-        return [
-            (ext.K_PAD_LAST, [self._ptr(x), scratch],
-             [n * H * W, C, c8], []),
-            (ext.K_CONV,
-             [scratch, wt8.data_ptr(), bias_ptr, res_ptr,
-              self.gm.zeros_ptr(), self._ptr(op.outputs[0])],
-             [n, H, W, c8, Kc, R, S, sh, sw, pt, pl, Ho, Wo, Kp8, act],
-             []),
-        ]
-
-    def _c_bgemm(self, op: PlanOp, ext):
-        p = op.params
-        a, b = op.inputs
-        a_shape = self.shapes[a]
-        b_shape = self.shapes[b]
-        if p.get("trans_a"):
-            raise RuntimeError("batched_gemm trans_a unsupported")
-        trans_b = bool(p.get("trans_b"))
-        M, K = a_shape[-2], a_shape[-1]
-        if trans_b:
-            N = b_shape[-2]
-        else:
-            N = b_shape[-1]
-        bat_a = int(np.prod(a_shape[:-2])) if len(a_shape) > 2 else 1
-        bat_b = int(np.prod(b_shape[:-2])) if len(b_shape) > 2 else 1
-        bat = max(bat_a, bat_b)
-        sA = M * K if bat_a > 1 else 0
-        sB = (b_shape[-1] * b_shape[-2]) if bat_b > 1 else 0
-        sC = M * N
-        return [(ext.K_BGEMM,
-                 [self._ptr(a), self._ptr(b), self._ptr(op.outputs[0])],
-                 [bat, M, N, K, sA, sB, sC, 1 if trans_b else 0],
-                 [1.0])]
 
     # -- runtime -----------------------------------------------------------
     def view(self, idx: int):
@@ -1216,21 +618,16 @@ class GpuModel:
         (~270 individual .to(device) calls cost 60-130 ms per ResNet-50
         cold load; this path is ~10 ms + one 100 MB transfer.)"""
         torch, _ = _load_backend()
-        float_ws = []
-        total = 0
-        self._int_idx = []
-        for t in self.plan.tensors:
-            if t.kind != "weight" or t.weight is None:
-                continue
-            w = t.weight
-            if w.dtype in (np.int32, np.int64):
-                self._weights[t.idx] = torch.from_numpy(
-                    np.ascontiguousarray(w.astype(np.int32))).to(self.device)
-                self._int_idx.append(t.idx)
-            else:
-                n = int(w.size)
-                float_ws.append((t.idx, w, total, n))
-                total += (n + 127) // 128 * 128   # keep 256B alignment
+        # the same layout call emission addresses the blob by
+        layout = blob_layout(self.plan)
+        tensors = self.plan.tensors
+        self._int_idx = layout.int_idx
+        for idx in layout.int_idx:
+            self._weights[idx] = torch.from_numpy(np.ascontiguousarray(
+                tensors[idx].weight.astype(np.int32))).to(self.device)
+        float_ws = [(idx, tensors[idx].weight, off, n)
+                    for idx, (off, n) in layout.slots.items()]
+        total = layout.total
         if not float_ws:
             return
         import os as _os
@@ -1338,8 +735,8 @@ class GpuModel:
                 _blob_cache_put(self.plan, cpu_blob)
         self._weight_blob = blob              # keep the allocation alive
         # LAZY views: ~270 torch view creations per cold load cost
-        # milliseconds; weight_ptr/master_weight materialize on demand
-        # (the template fast path needs neither)
+        # milliseconds; master_weight materializes on demand (a context
+        # addresses the blob by offset and needs no view)
         self._blob_slots = {idx: (off, n, tuple(w.shape))
                             for idx, w, off, n in float_ws}
 
@@ -1360,15 +757,6 @@ class GpuModel:
     def has_master_weight(self, idx: int) -> bool:
         return idx in self._weights or \
             idx in getattr(self, "_blob_slots", {})
-
-    def weight_ptr(self, idx: int) -> int:
-        t = self._weights.get(idx)
-        if t is not None:
-            return t.data_ptr()
-        slot = getattr(self, "_blob_slots", {}).get(idx)
-        if slot is not None:
-            return self._weight_blob.data_ptr() + slot[0] * 2
-        return self._weights[idx].data_ptr()    # raises KeyError
 
     def zeros_ptr(self) -> int:
         """A small zeroed device buffer used as the gather source for
@@ -1484,15 +872,13 @@ class GpuModel:
 
     # -- transform arena / relocation regions ------------------------------
     def _region_items(self):
-        """[(key, tensor)] for every device weight region a context's
-        emitted calls can point into (master blob excluded — it has its
-        own entry)."""
+        """[(key, tensor)] of the weight regions the transform arena
+        snapshots: int weights and every materialised transform."""
         items = []
         for idx in getattr(self, "_int_idx", []):
             items.append((("int", idx), self._weights[idx]))
         for k, t in self._gemm_weights.items():
-            items.append((("gw",) + tuple(k) if isinstance(k, tuple)
-                          else ("gw", k), t))
+            items.append((("gw",) + k, t))
         for k, t in self._conv_weights.items():
             kk = k if isinstance(k, tuple) else (k,)
             items.append((("cw",) + kk, t))
@@ -1501,34 +887,46 @@ class GpuModel:
             items.append((("f8s",) + tuple(k), sc))
         return items
 
-    def region_list(self):
-        """[(base, size, key)] for pointer classification."""
-        out = []
-        blob = getattr(self, "_weight_blob", None)
-        if blob is not None:
-            out.append((blob.data_ptr(),
-                        blob.numel() * blob.element_size(), ("blob",)))
-        for key, t in self._region_items():
-            out.append((t.data_ptr(), t.numel() * t.element_size(), key))
-        out.append((self.zeros_ptr(), 64, ("zeros",)))
-        return out
+    def n_transforms(self) -> int:
+        """How many weight transforms this model holds as tensors."""
+        return len(self._gemm_weights) + len(self._conv_weights) + \
+            len(self._gemm_weights_fp8)
 
-    def region_bases(self):
-        """key -> device base pointer for template instantiation."""
-        bases = {}
-        blob = getattr(self, "_weight_blob", None)
-        if blob is not None:
-            bases[("blob",)] = blob.data_ptr()
+    def region_bases(self, keys) -> List[int]:
+        """Device base address of each weight region a call template
+        names by key (engine/emit.py lists the keys). A region comes
+        from the restored arena when the model has one (one dict lookup
+        per key: this runs on every cold load), else from _region_ptr."""
         arena = getattr(self, "_arena_dev", None)
-        if arena is not None:
-            base = arena.data_ptr()
-            for key, (_k, off, _nb, _dt, _sh) in \
-                    getattr(self, "_arena_entries", {}).items():
-                bases[key] = base + off
-        for key, t in self._region_items():
-            bases[key] = t.data_ptr()
-        bases[("zeros",)] = self.zeros_ptr()
+        entries = self._arena_entries if arena is not None else {}
+        arena_base = arena.data_ptr() if arena is not None else 0
+        bases = []
+        for key in keys:
+            ent = entries.get(key)
+            bases.append(arena_base + ent[1] if ent is not None
+                         else self._region_ptr(key))
         return bases
+
+    def _region_ptr(self, key: tuple) -> int:
+        """A region outside the arena; a transform is materialised on
+        demand."""
+        kind = key[0]
+        if kind == "blob":
+            return self._weight_blob.data_ptr()
+        if kind == "zeros":
+            return self.zeros_ptr()
+        if kind == "int":
+            return self._weights[key[1]].data_ptr()
+        if kind == "gw":
+            return self.gemm_weight(key[1], key[2]).data_ptr()
+        if kind == "cw" and len(key) == 2:
+            return self.conv_weight(key[1]).data_ptr()
+        if kind == "cw" and key[2] == "cpad":
+            return self.conv_weight_cpad(key[1], key[3]).data_ptr()
+        if kind in ("f8q", "f8s"):
+            q, scale = self.gemm_weight_fp8(key[1], key[2])
+            return (q if kind == "f8q" else scale).data_ptr()
+        raise KeyError(f"unknown weight region {key}")
 
     def publish_transform_arena(self) -> None:
         """Snapshot this model's transformed weights into a pinned host
@@ -1576,12 +974,12 @@ class GpuModel:
                 dev_arena.copy_(pinned, non_blocking=True)
         self._arena_dev = dev_arena
         # LAZY views: region_bases() computes pointers straight from
-        # the entry offsets; tensor views materialize only if the
-        # (rare) full-emit path asks for a transform. ~300 eager view
+        # the entry offsets; tensor views materialize only if someone
+        # asks an accessor for the transform itself. ~300 eager view
         # creations per cold load were milliseconds of Python.
         self._arena_entries = {tuple(e[0]): e for e in entries}
-        # int weights ARE needed eagerly (emit reads _weights[idx]) and
-        # are few
+        # int weights live in the arena from here on (master_weight
+        # reads _weights[idx]); they are few
         for key, off, nb, dt, shape in entries:
             if key[0] == "int":
                 self._weights[key[1]] = \
