@@ -132,13 +132,15 @@ static void launch_call(const Call& c, hipStream_t s) {
       break;
     case K_CONV: {
       // ptrs: [x, w, bias, residual|0, zeros, y]
-      // ints: [N,H,W,C,Kc,R,S,sh,sw,pt,pl,Ho,Wo,k_pad,act]
+      // ints: [N,H,W,C,Kc,R,S,sh,sw,pt,pl,Ho,Wo,k_pad,act(,groups)];
+      // the 15-int form is a dense conv
       const ushort* res = c.ptrs[3] ? cp(3) : nullptr;
       launch_conv_igemm(s, cp(0), cp(1), cp(2), res, cp(4), p(5),
                         int(I[0]), int(I[1]), int(I[2]), int(I[3]),
                         int(I[4]), int(I[5]), int(I[6]), int(I[7]),
                         int(I[8]), int(I[9]), int(I[10]), int(I[11]),
-                        int(I[12]), int(I[13]), int(I[14]));
+                        int(I[12]), int(I[13]), int(I[14]),
+                        I.size() > 15 ? int(I[15]) : 1);
       break;
     }
     case K_PAD_LAST:

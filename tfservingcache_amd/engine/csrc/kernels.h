@@ -98,12 +98,17 @@ void launch_batched_gemm(hipStream_t s, const ushort* A, const ushort* B,
 // A-tile gather happens in the GEMM's LDS staging (per-lane source
 // address from the conv geometry; out-of-image patches read from
 // `zeros`, a >=16-byte zeroed device buffer).
+// groups > 1 is a grouped conv on its own kernel: group g reads input
+// channels g*Cg.. (Cg = C/groups, Cg % 8 == 0) and writes output
+// channels g*Ng.. (Ng = Kc/groups, Ng % 8 == 0); w is
+// [Kc][pad64(R*S*Cg)], row g*Ng + n being group g's filter n, and
+// k_pad = pad64(R*S*Cg).
 void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        const ushort* bias, const ushort* residual,
                        const ushort* zeros, ushort* y,
                        int N, int H, int W, int C, int Kc, int R, int S,
                        int sh, int sw, int pt, int pl, int Ho, int Wo,
-                       int k_pad, int act);
+                       int k_pad, int act, int groups = 1);
 
 // im2col for NHWC conv: out[N*Ho*Wo, K_pad] where the first R*S*C columns
 // hold the patch elements (r,s,c order, c fastest) and columns >= R*S*C

@@ -487,12 +487,265 @@ void conv_igemm_kernel(const ushort* __restrict__ x,
                                 m0, n0, wave, lane, wm, wn, act, 1.0f);
 }
 
+// ---------------------------------------------------------------------------
+// Grouped implicit-GEMM conv (ResNeXt / RegNet): per group g the GEMM is
+//   y[M, g*Ng .. g*Ng+Ng) = x_g[M, pad64(R*S*Cg)] x w[g*Ng .., :]^T
+// with x_g the im2col of input channels g*Cg .. g*Cg+Cg. One block owns
+// (M tile, N tile inside the group, group). Ng is small (16..64 after
+// the planner's merge), so the tile is 128 x (16*NT): the four waves
+// stack along M, 32 rows x BN columns each. Same anatomy as the dense
+// kernel: 16-byte glds staging with the XOR source swizzle, two LDS
+// buffers, one barrier per K tile, 16x16x32 bf16 MFMA, LDS-restaged
+// coalesced epilogue. With NT = 1 an A fragment feeds one MFMA, so the
+// kernel is gather- and LDS-bound, not MFMA-bound.
+// ---------------------------------------------------------------------------
+struct GroupedConvGeom {
+  int H, W, C, Cg, Ng, R, S, sh, sw, pt, pl, Ho, Wo, rsc;   // rsc = R*S*Cg
+};
+
+constexpr int GBM = 128;                  // grouped kernel's M tile
+
+// B tile: rows n0 .. n0+BN_ of group g's filters ([Kc][ld] weight, rows
+// g*Ng + n), clamped to the group's last row. BN_/8 glds of 8 rows each,
+// dealt round-robin to the four waves (BN_ = 16: waves 0 and 1 only).
+template <int BN_>
+TFSC_DEV void stage_tile_grouped_b(const ushort* __restrict__ w, int ld,
+                                   int row_base, int row_limit, int n0,
+                                   int k0, char* lds_tile, int wave,
+                                   int lane) {
+  int r_in = lane >> 3;
+  int chunk = lane & 7;
+  #pragma unroll
+  for (int i = 0; i < (BN_ / 8 + N_WAVES - 1) / N_WAVES; ++i) {
+    int slab = i * N_WAVES + wave;        // wave-uniform
+    if (slab * 8 >= BN_) break;
+    int row = slab * 8 + r_in;
+    int n = n0 + row;
+    n = n < row_limit ? n : row_limit;
+    int chunk_src = chunk ^ (row & 7);
+    const ushort* gptr =
+        w + (int64_t)(row_base + n) * ld + k0 + chunk_src * 8;
+    __builtin_amdgcn_global_load_lds(
+        reinterpret_cast<const uint32_t*>(gptr),
+        reinterpret_cast<uint32_t*>(lds_tile + slab * 8 * 128), 16, 0, 0);
+  }
+}
+
+template <int NT, bool HAS_RES>
+__global__ __launch_bounds__(THREADS)
+void conv_igemm_grouped_kernel(const ushort* __restrict__ x,
+                               const ushort* __restrict__ B,
+                               const ushort* __restrict__ bias,
+                               const ushort* __restrict__ residual,
+                               const ushort* __restrict__ zeros,
+                               ushort* __restrict__ y,
+                               int M, int Kc, int K, int act,
+                               GroupedConvGeom g, int groups, int n_tiles_n) {
+  constexpr int BN_ = 16 * NT;
+  constexpr int A_BYTES = GBM * BK * 2, B_BYTES = BN_ * BK * 2;
+  __shared__ __attribute__((aligned(16))) char smem[2 * (A_BYTES + B_BYTES)];
+  auto lds_a = [&](int buf) -> char* {
+    return smem + buf * (A_BYTES + B_BYTES); };
+  auto lds_b = [&](int buf) -> char* {
+    return smem + buf * (A_BYTES + B_BYTES) + A_BYTES; };
+
+  // group fastest: the groups of one M tile read the same pixels (a
+  // 128-byte line holds several groups' channels), so they should run
+  // together on one XCD's L2
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int grp = bid % groups;
+  const int t_ = bid / groups;
+  const int n0 = (t_ % n_tiles_n) * BN_;  // within the group
+  const int m0 = (t_ / n_tiles_n) * GBM;
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int r_in = lane >> 3;
+  const int chunk_src = (lane & 7) ^ r_in;    // row & 7 == r_in
+
+  // the lane's four A rows never change: decompose m -> (n, ho, wo) once
+  int hi0[4], wi0[4], nH[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int m = m0 + wave * 32 + i * 8 + r_in;
+    m = m < M - 1 ? m : M - 1;
+    int wo = m % g.Wo;
+    int t = m / g.Wo;
+    hi0[i] = (t % g.Ho) * g.sh - g.pt;
+    wi0[i] = wo * g.sw - g.pl;
+    nH[i] = (t / g.Ho) * g.H;
+  }
+  const ushort* xg = x + grp * g.Cg;
+
+  auto stage_a = [&](int k0, char* lds_tile) {
+    int k = k0 + chunk_src * 8;           // start of the 8-channel chunk
+    int c = k % g.Cg;
+    int t2 = k / g.Cg;
+    int s = t2 % g.S;
+    int r = t2 / g.S;
+    bool k_ok = k < g.rsc;
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int hi = hi0[i] + r, wi = wi0[i] + s;
+      bool ok = k_ok & (hi >= 0) & (hi < g.H) & (wi >= 0) & (wi < g.W);
+      const ushort* gptr = ok
+          ? xg + ((int64_t)(nH[i] + hi) * g.W + wi) * g.C + c
+          : zeros;
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const uint32_t*>(gptr),
+          reinterpret_cast<uint32_t*>(lds_tile + (wave * 32 + i * 8) * 128),
+          16, 0, 0);
+    }
+  };
+
+  f32x4_t acc[2][NT] = {};
+  const int n_ktiles = K / BK;
+  const int row_base = grp * g.Ng;
+
+  stage_a(0, lds_a(0));
+  stage_tile_grouped_b<BN_>(B, K, row_base, g.Ng - 1, n0, 0, lds_b(0), wave,
+                            lane);
+
+  int cur = 0;
+  for (int kt = 0; kt < n_ktiles; ++kt) {
+    __syncthreads();
+    if (kt + 1 < n_ktiles) {
+      int k0 = (kt + 1) * BK;
+      stage_a(k0, lds_a(cur ^ 1));
+      stage_tile_grouped_b<BN_>(B, K, row_base, g.Ng - 1, n0, k0,
+                                lds_b(cur ^ 1), wave, lane);
+    }
+    const char* at = lds_a(cur);
+    const char* bt = lds_b(cur);
+    const int frow = lane & 15;
+    const int kgrp = lane >> 4;
+    #pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8_t a_frag[2], b_frag[NT];
+      const int chunk = ks * 4 + kgrp;
+      #pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+        a_frag[mi] = *reinterpret_cast<const bf16x8_t*>(
+            at + lds_off(wave * 32 + mi * 16 + frow, chunk));
+      #pragma unroll
+      for (int ni = 0; ni < NT; ++ni)
+        b_frag[ni] = *reinterpret_cast<const bf16x8_t*>(
+            bt + lds_off(ni * 16 + frow, chunk));
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < NT; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_frag[mi], b_frag[ni], acc[mi][ni], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    cur ^= 1;
+  }
+
+  // epilogue: each wave restages its 32 x BN_ tile (acc + bias, f32: the
+  // narrow tile leaves room, so the result is rounded to bf16 once,
+  // after residual and activation) through its own LDS region and
+  // streams it out in 16-byte chunks to y[row*Kc + grp*Ng + n0 + col];
+  // the column bound is the group's Ng (whole chunks, Ng % 8 == 0), the
+  // row bound M
+  __syncthreads();              // tiles are dead; reuse as staging
+  float* stage = reinterpret_cast<float*>(smem + wave * (32 * BN_ * 4));
+  {
+    const int col_in = lane & 15;
+    const int row_b = (lane >> 4) * 4;
+    #pragma unroll
+    for (int ni = 0; ni < NT; ++ni) {
+      int col = ni * 16 + col_in;
+      int nc = n0 + col;
+      nc = nc < g.Ng ? nc : g.Ng - 1;
+      float bv = bf2f(bias[row_base + nc]);
+      #pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r)
+          stage[(mi * 16 + row_b + r) * BN_ + col] = acc[mi][ni][r] + bv;
+    }
+  }
+  __syncthreads();
+  constexpr int CPR = BN_ / 8;            // 16-byte chunks per row
+  #pragma unroll
+  for (int i = 0; i < NT; ++i) {          // 32*CPR chunks = NT x 64 lanes
+    int chunk_id = i * 64 + lane;
+    int row = chunk_id / CPR;
+    int chunk = chunk_id % CPR;
+    int grow = m0 + wave * 32 + row;
+    int gcol = n0 + chunk * 8;
+    if (grow >= M || gcol >= g.Ng) continue;
+    const f32x4_t* sp =
+        reinterpret_cast<const f32x4_t*>(stage + row * BN_ + chunk * 8);
+    f32x4_t lo = sp[0], hi = sp[1];
+    int64_t goff = (int64_t)grow * Kc + row_base + gcol;
+    bf16x8 rv = {};
+    if (HAS_RES) rv = *reinterpret_cast<const bf16x8*>(residual + goff);
+    bf16x8 v;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float xv = j < 4 ? lo[j] : hi[j - 4];
+      if (HAS_RES) xv += bf2f((ushort)rv[j]);
+      v[j] = (short)f2bf(act_apply(xv, act));
+    }
+    *reinterpret_cast<bf16x8*>(y + goff) = v;
+  }
+}
+
+template <int NT>
+static void conv_grouped_launch(hipStream_t s, const ushort* x,
+                                const ushort* w, const ushort* bias,
+                                const ushort* residual, const ushort* zeros,
+                                ushort* y, int M, int Kc, int k_pad, int act,
+                                const GroupedConvGeom& g, int groups) {
+  int ntm = int(ceil_div(M, GBM)), ntn = int(ceil_div(g.Ng, 16 * NT));
+  dim3 grid(ntm * ntn * groups);
+  if (residual)
+    hipLaunchKernelGGL((conv_igemm_grouped_kernel<NT, true>), grid,
+                       dim3(THREADS), 0, s, x, w, bias, residual, zeros, y,
+                       M, Kc, k_pad, act, g, groups, ntn);
+  else
+    hipLaunchKernelGGL((conv_igemm_grouped_kernel<NT, false>), grid,
+                       dim3(THREADS), 0, s, x, w, bias, nullptr, zeros, y,
+                       M, Kc, k_pad, act, g, groups, ntn);
+}
+
 void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        const ushort* bias, const ushort* residual,
                        const ushort* zeros, ushort* y,
                        int N_img, int H, int W, int C, int Kc, int R,
                        int S, int sh, int sw, int pt, int pl, int Ho,
-                       int Wo, int k_pad, int act) {
+                       int Wo, int k_pad, int act, int groups) {
+  if (groups < 1)
+    throw std::runtime_error("conv_igemm groups must be >= 1");
+  if (groups > 1) {
+    if (C % groups != 0 || Kc % groups != 0)
+      throw std::runtime_error(
+          "grouped conv_igemm: groups must divide C and Kc");
+    int Cg = C / groups, Ng = Kc / groups;
+    if (Cg % 8 != 0 || Ng % 8 != 0)
+      throw std::runtime_error(
+          "grouped conv_igemm requires (C/groups) % 8 == 0 and "
+          "(Kc/groups) % 8 == 0");
+    if (k_pad != (R * S * Cg + BK - 1) / BK * BK)
+      throw std::runtime_error(
+          "grouped conv_igemm k_pad must be pad64(R*S*C/groups)");
+    GroupedConvGeom g{H, W, C, Cg, Ng, R, S, sh, sw, pt, pl, Ho, Wo,
+                      R * S * Cg};
+    int M = N_img * Ho * Wo;
+    // narrowest N tile that covers the group; Ng > 64 takes several
+    if (Ng <= 16)
+      conv_grouped_launch<1>(s, x, w, bias, residual, zeros, y, M, Kc,
+                             k_pad, act, g, groups);
+    else if (Ng <= 32)
+      conv_grouped_launch<2>(s, x, w, bias, residual, zeros, y, M, Kc,
+                             k_pad, act, g, groups);
+    else
+      conv_grouped_launch<4>(s, x, w, bias, residual, zeros, y, M, Kc,
+                             k_pad, act, g, groups);
+    return;
+  }
   if (C % 8 != 0)
     throw std::runtime_error("conv_igemm requires C % 8 == 0");
   if (k_pad % BK != 0)

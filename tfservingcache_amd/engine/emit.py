@@ -11,6 +11,7 @@ a kernel call takes is written as a descriptor, never an address:
         ("int", idx)                int32 weight tensor idx
         ("gw", idx, trans_b)        pre-transposed GEMM weight
         ("cw", idx)                 conv weight [Kc][pad64(R*S*C)]
+                                    (grouped: C is the group's Cg)
         ("cw", idx, "cpad", c8)     conv weight, input channels widened
         ("f8q"|"f8s", idx, trans_b) fp8 GEMM weight bytes / row scales
         ("zeros",)                  small zeroed buffer (conv gather)
@@ -558,7 +559,18 @@ class _Emitter:
         act = _act(p)
         out = self._ptr(op.outputs[0])
         zeros = (("zeros",), 0)
-        if R == 1 and S == 1 and (sh, sw) == (1, 1) and \
+        groups = p.get("groups", 1)
+        if groups > 1:
+            # grouped implicit-GEMM: the master is [R,S,Cg,K] (Cg % 8 ==
+            # 0 by the planner's merge rule), C the input's full channel
+            # count; groups rides as an optional 16th int. Never the
+            # 1x1 GEMM shortcut or the channel widening.
+            self._call("CONV",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res,
+                        zeros, out],
+                       [n, H, W, C, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                        _pad64(wR * wS * wC), act, groups])
+        elif R == 1 and S == 1 and (sh, sw) == (1, 1) and \
                 (pt, pb, pl, pr) == (0, 0, 0, 0) and C % 64 == 0:
             self._call("GEMM",
                        [self._ptr(x), (("cw", w_idx), 0), bias, res, out],

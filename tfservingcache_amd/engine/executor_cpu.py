@@ -300,13 +300,31 @@ class CpuExecutor:
         N = x.shape[0]
         Ho, Wo = p["out_hw"]
         xp = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
-        # im2col
-        cols = np.empty((N, Ho, Wo, R * S * C), dtype=np.float32)
-        for r in range(R):
-            for s in range(S):
-                patch = xp[:, r:r + sh * Ho:sh, s:s + sw * Wo:sw, :]
-                cols[..., (r * S + s) * C:(r * S + s + 1) * C] = patch
-        y = cols.reshape(-1, R * S * C) @ w.reshape(-1, K)
+        G = p.get("groups", 1)
+        if G == 1:
+            # im2col
+            cols = np.empty((N, Ho, Wo, R * S * C), dtype=np.float32)
+            for r in range(R):
+                for s in range(S):
+                    patch = xp[:, r:r + sh * Ho:sh, s:s + sw * Wo:sw, :]
+                    cols[..., (r * S + s) * C:(r * S + s + 1) * C] = patch
+            y = cols.reshape(-1, R * S * C) @ w.reshape(-1, K)
+        else:
+            # grouped: w is [R,S,Cg,K]; group g reads input channels
+            # g*Cg.. and writes output channels g*Ng..
+            Ng = K // G
+            ys = []
+            for gi in range(G):
+                cols = np.empty((N, Ho, Wo, R * S * C), dtype=np.float32)
+                for r in range(R):
+                    for s in range(S):
+                        patch = xp[:, r:r + sh * Ho:sh, s:s + sw * Wo:sw,
+                                   gi * C:(gi + 1) * C]
+                        cols[..., (r * S + s) * C:(r * S + s + 1) * C] = \
+                            patch
+                ys.append(cols.reshape(-1, R * S * C) @
+                          w[..., gi * Ng:(gi + 1) * Ng].reshape(-1, Ng))
+            y = np.concatenate(ys, axis=1)
         y = y.reshape(N, Ho, Wo, K) + b
         ni = 3
         if p.get("residual"):
