@@ -196,12 +196,14 @@ static void launch_call(const Call& c, hipStream_t s) {
       break;
     case K_DEPTHWISE:
       // ptrs: [x, w, bias, y]
-      // ints: [N,H,W,C,R,S,sh,sw,pt,pl,Ho,Wo,act]
+      // ints: [N,H,W,C,R,S,sh,sw,pt,pl,Ho,Wo,act] and an optional
+      // 14th, the depth multiplier M (absent = 1); C is the INPUT
+      // channel count, w / bias / y have C*M channels
       launch_depthwise_conv(s, cp(0), cp(1), cp(2), p(3), int(I[0]),
                             int(I[1]), int(I[2]), int(I[3]), int(I[4]),
                             int(I[5]), int(I[6]), int(I[7]), int(I[8]),
                             int(I[9]), int(I[10]), int(I[11]),
-                            int(I[12]));
+                            int(I[12]), I.size() > 13 ? int(I[13]) : 1);
       break;
     case K_RESIZE: {
       // ptrs: [x, y]

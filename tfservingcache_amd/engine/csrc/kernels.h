@@ -120,17 +120,27 @@ void launch_im2col(hipStream_t s, const ushort* x, ushort* y,
                    int sh, int sw, int pt, int pl, int Ho, int Wo,
                    int k_pad);
 
-// Depthwise NHWC conv (depth_multiplier == 1, MobileNet-class):
+// Depthwise NHWC conv (MobileNet-class). With depth_multiplier == 1:
 //   y[n,ho,wo,c] = act(sum_{r,s} x[n, ho*sh-pt+r, wo*sw-pl+s, c] * w[r,s,c]
 //                      + bias[c])
 // Memory-bound (no MFMA shape): vectorized 4x bf16 over the contiguous
 // channel dim, grid-stride over N*Ho*Wo*C/4. w is the [R,S,C,1] master
 // read as flat [R*S*C].
+// mult > 1 is the depth multiplier M (K_DEPTHWISE's optional 14th int):
+// C stays the INPUT channel count, and w [R,S,C*M], bias [C*M] and
+// y [N,Ho,Wo,C*M] are indexed by k = c*M + m (the TF [R,S,C,M] filter
+// read flat), output channel k reading input channel k / M:
+//   y[n,ho,wo,k] = act(sum_{r,s} x[n, ho*sh-pt+r, wo*sw-pl+s, k/M]
+//                      * w[r,s,k] + bias[k])
+// 8 output channels (16 bytes) per thread when (C*M) % 8 == 0 and
+// M in {2,4} or M % 8 == 0, one output element per thread otherwise.
+// mult == 1 runs exactly the kernels described above. Throws on
+// mult < 1 before any launch.
 void launch_depthwise_conv(hipStream_t s, const ushort* x, const ushort* w,
                            const ushort* bias, ushort* y,
                            int N, int H, int W, int C, int R, int S,
                            int sh, int sw, int pt, int pl, int Ho, int Wo,
-                           int act);
+                           int act, int mult = 1);
 
 // NHWC image resize with TF's coordinate rules (ResizeNearestNeighbor /
 // ResizeBilinear): mode 0 = nearest, 1 = bilinear. The per-axis scale is

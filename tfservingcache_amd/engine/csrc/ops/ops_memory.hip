@@ -655,10 +655,11 @@ void launch_pad_nhwc(hipStream_t s, const ushort* x, ushort* y,
 }
 
 // ---------------------------------------------------------------------------
-// depthwise NHWC conv (depth_multiplier == 1): per-channel R x S taps,
+// depthwise NHWC conv: per-channel R x S taps,
 // memory-bound — channels are contiguous in NHWC so the channel dim is
 // the vector dim (4x bf16). w is [R,S,C] flat; per-tap weight loads hit
-// L2 (w is tiny and every pixel of the image reuses it).
+// L2 (w is tiny and every pixel of the image reuses it). These two
+// kernels are depth_multiplier == 1; the multiplier kernels follow them.
 // ---------------------------------------------------------------------------
 TFSC_DEV float dw_act(float v, int act) {
   switch (act) {
@@ -748,11 +749,147 @@ __global__ void k_depthwise_scalar(const ushort* __restrict__ x,
   }
 }
 
+// Depth multiplier M > 1: output channel k = c*M + m reads input channel
+// c = k / M; w [R,S,C*M], bias [C*M] and y [N,Ho,Wo,C*M] are contiguous
+// in k (the TF [R,S,C,M] filter read flat). Still memory-bound: k is
+// the vector dim, 8 bf16 = 16 bytes of w, bias and y per thread.
+//
+// XC = 8/M input channels feed one thread's 8 outputs: 4 (M = 2, one
+// 8-byte x load per tap), 2 (M = 4, one 4-byte load) or 1 (M % 8 == 0,
+// one bf16 shared by all 8). The launcher only comes here when
+// (C*M) % 8 == 0 and M is 2, 4 or a multiple of 8, and that is what
+// aligns the x loads: a pixel's row of C elements starts at a multiple
+// of 8 bytes when C % 4 == 0 (M = 2) and of 4 bytes when C % 2 == 0
+// (M = 4), and the thread's first channel kv*XC sits XC*2 bytes further
+// per vector; for M % 8 == 0 the 8 outputs kv*8.. lie inside one block
+// of M and share the single channel kv*8 / M.
+template <int XC>
+__global__ void k_depthwise_mult_v8(const ushort* __restrict__ x,
+                                    const ushort* __restrict__ w,
+                                    const ushort* __restrict__ bias,
+                                    ushort* __restrict__ y,
+                                    int N, int H, int W, int C, int M,
+                                    int R, int S, int sh, int sw, int pt,
+                                    int pl, int Ho, int Wo, int act) {
+  int K = C * M;
+  int k8 = K / 8;
+  int64_t total = (int64_t)N * Ho * Wo * k8;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < total; i += stride) {
+    int64_t t = i;
+    int kv = int(t % k8); t /= k8;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    int c0 = XC == 1 ? (kv * 8) / M : kv * XC;
+    float acc[8];
+    short8_t bv = reinterpret_cast<const short8_t*>(bias)[kv];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bf2f((ushort)bv[j]);
+    int hi0 = ho * sh - pt, wi0 = wo * sw - pl;
+    for (int r = 0; r < R; ++r) {
+      int hi = hi0 + r;
+      if (hi < 0 || hi >= H) continue;
+      for (int sx = 0; sx < S; ++sx) {
+        int wi = wi0 + sx;
+        if (wi < 0 || wi >= W) continue;
+        const ushort* xp = x + ((((int64_t)n * H + hi) * W + wi) * C + c0);
+        float xf[XC];
+        if constexpr (XC == 4) {
+          short4_t xv = *reinterpret_cast<const short4_t*>(xp);
+          #pragma unroll
+          for (int j = 0; j < 4; ++j) xf[j] = bf2f((ushort)xv[j]);
+        } else if constexpr (XC == 2) {
+          uint32_t xv = *reinterpret_cast<const uint32_t*>(xp);
+          xf[0] = bf2f((ushort)(xv & 0xffffu));
+          xf[1] = bf2f((ushort)(xv >> 16));
+        } else {
+          xf[0] = bf2f(*xp);
+        }
+        short8_t wv = reinterpret_cast<const short8_t*>(
+            w + ((int64_t)(r * S + sx) * K))[kv];
+        #pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc[j] += xf[j / (8 / XC)] * bf2f((ushort)wv[j]);
+      }
+    }
+    short8_t out;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j)
+      out[j] = (short)f2bf(dw_act(acc[j], act));
+    reinterpret_cast<short8_t*>(
+        y + ((((int64_t)n * Ho + ho) * Wo + wo) * K))[kv] = out;
+  }
+}
+
+// every other (C, M): one thread per output element
+__global__ void k_depthwise_mult_scalar(const ushort* __restrict__ x,
+                                        const ushort* __restrict__ w,
+                                        const ushort* __restrict__ bias,
+                                        ushort* __restrict__ y,
+                                        int N, int H, int W, int C, int M,
+                                        int R, int S, int sh, int sw,
+                                        int pt, int pl, int Ho, int Wo,
+                                        int act) {
+  int K = C * M;
+  int64_t total = (int64_t)N * Ho * Wo * K;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < total; i += stride) {
+    int64_t t = i;
+    int k = int(t % K); t /= K;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    int c = k / M;
+    float acc = bf2f(bias[k]);
+    int hi0 = ho * sh - pt, wi0 = wo * sw - pl;
+    for (int r = 0; r < R; ++r) {
+      int hi = hi0 + r;
+      if (hi < 0 || hi >= H) continue;
+      for (int sx = 0; sx < S; ++sx) {
+        int wi = wi0 + sx;
+        if (wi < 0 || wi >= W) continue;
+        acc += bf2f(x[(((int64_t)n * H + hi) * W + wi) * C + c]) *
+               bf2f(w[(int64_t)(r * S + sx) * K + k]);
+      }
+    }
+    y[i] = f2bf(dw_act(acc, act));
+  }
+}
+
 void launch_depthwise_conv(hipStream_t s, const ushort* x, const ushort* w,
                            const ushort* bias, ushort* y,
                            int N, int H, int W, int C, int R, int S,
                            int sh, int sw, int pt, int pl, int Ho, int Wo,
-                           int act) {
+                           int act, int mult) {
+  if (mult < 1)
+    throw std::runtime_error("depthwise conv: depth multiplier " +
+                             std::to_string(mult) + " < 1");
+  if (mult > 1) {
+    int64_t K = (int64_t)C * mult;
+    bool vec = K % 8 == 0 && (mult == 2 || mult == 4 || mult % 8 == 0);
+    if (!vec) {
+      hipLaunchKernelGGL(k_depthwise_mult_scalar,
+                         dim3(grid_for((int64_t)N * Ho * Wo * K)),
+                         dim3(TPB), 0, s, x, w, bias, y, N, H, W, C, mult,
+                         R, S, sh, sw, pt, pl, Ho, Wo, act);
+      return;
+    }
+    dim3 grid(grid_for((int64_t)N * Ho * Wo * (K / 8)));
+    if (mult == 2)
+      hipLaunchKernelGGL(k_depthwise_mult_v8<4>, grid, dim3(TPB), 0, s, x,
+                         w, bias, y, N, H, W, C, mult, R, S, sh, sw, pt,
+                         pl, Ho, Wo, act);
+    else if (mult == 4)
+      hipLaunchKernelGGL(k_depthwise_mult_v8<2>, grid, dim3(TPB), 0, s, x,
+                         w, bias, y, N, H, W, C, mult, R, S, sh, sw, pt,
+                         pl, Ho, Wo, act);
+    else
+      hipLaunchKernelGGL(k_depthwise_mult_v8<1>, grid, dim3(TPB), 0, s, x,
+                         w, bias, y, N, H, W, C, mult, R, S, sh, sw, pt,
+                         pl, Ho, Wo, act);
+    return;
+  }
   if (C % 4 == 0) {
     int64_t total = (int64_t)N * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(k_depthwise_v4, dim3(grid_for(total)), dim3(TPB),

@@ -336,8 +336,12 @@ class _Emitter:
                 R, S, _C = p["rsc"]
                 sh, sw = p["stride"]
                 pt, _pb, pl, _pr = p["pads"]
-                call("DEPTHWISE", io(op, 3),
-                     [n, h, w, c, R, S, sh, sw, pt, pl, ho, wo, _act(p)])
+                ints = [n, h, w, c, R, S, sh, sw, pt, pl, ho, wo, _act(p)]
+                if p.get("mult", 1) > 1:
+                    # optional 14th int, like CONV's 16th `groups`:
+                    # c stays the INPUT channel count
+                    ints.append(p["mult"])
+                call("DEPTHWISE", io(op, 3), ints)
             elif k in _ROWWISE:
                 call(_ROWWISE[k], io(op, 1), _rows_cols(xs))
             elif k == "layernorm":

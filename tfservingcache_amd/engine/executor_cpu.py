@@ -333,19 +333,23 @@ class CpuExecutor:
 
     def _depthwise(self, op: PlanOp, _get, vals) -> None:
         x = _get(op.inputs[0])          # [N,H,W,C]
-        w = _get(op.inputs[1])          # [R,S,C]
-        b = _get(op.inputs[2])          # [C]
+        w = _get(op.inputs[1])          # [R,S,C*M], k = c*M + m
+        b = _get(op.inputs[2])          # [C*M]
         p = op.params
         sh, sw = p["stride"]
         pt, pb, pl, pr = p["pads"]
-        R, S, C = w.shape
+        R, S, K = w.shape
+        M = p.get("mult", 1)
         N = x.shape[0]
         Ho, Wo = p["out_hw"]
         xp = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
-        y = np.zeros((N, Ho, Wo, C), dtype=np.float32)
+        y = np.zeros((N, Ho, Wo, K), dtype=np.float32)
         for r in range(R):
             for s_ in range(S):
                 patch = xp[:, r:r + sh * Ho:sh, s_:s_ + sw * Wo:sw, :]
+                if M > 1:
+                    # each input channel feeds M consecutive outputs
+                    patch = np.repeat(patch, M, axis=-1)
                 y += patch * w[r, s_]
         y = y + b
         vals[op.outputs[0]] = _act(y, p.get("act", "none")).astype(

@@ -728,19 +728,26 @@ class _Lowerer:
         return G
 
     def lower_depthwise(self, nd: g.NodeDef, out: str) -> None:
-        """DepthwiseConv2dNative (MobileNet-class), depth_multiplier==1.
+        """DepthwiseConv2dNative (MobileNet-class), any depth_multiplier.
         Per-channel R x S taps — no MFMA shape, lowered to the dedicated
         memory-bound kernel (csrc/ops/ops_memory.hip depthwise). BN and
-        Relu/Relu6 consumers fold into the kernel like Conv2D."""
+        Relu/Relu6 consumers fold into the kernel like Conv2D.
+
+        The TF filter is [R,S,C,M]: output channel k = c*M + m reads
+        input channel c = k // M, so the filter read flat as [R,S,C*M]
+        is already in k order. The op carries that (R,S,C*M) weight, a
+        (C*M,) bias, rsc = (R,S,C) with C the INPUT channels, and a
+        `mult` key only when M > 1 (the golden call templates pin the
+        M == 1 op's params, keys and order)."""
         x_ref, w_ref = nd.input[0], nd.input[1]
         x = self.tid(x_ref)
         if _attr_s(nd, "data_format", "NHWC") != "NHWC":
             raise PlanError("only NHWC DepthwiseConv2dNative supported")
         w = np.asarray(self.weight_of(w_ref), dtype=np.float32)  # [R,S,C,M]
         R, S, Cin, M = w.shape
-        if M != 1:
-            raise PlanError(
-                f"depth_multiplier {M} unsupported (only 1)")
+        if M < 1:
+            raise PlanError(f"depth_multiplier {M} unsupported")
+        K = Cin * M
         dil = _attr_ints(nd, "dilations") or [1, 1, 1, 1]
         if any(d != 1 for d in dil):
             raise PlanError(f"dilated depthwise conv unsupported ({dil})")
@@ -758,6 +765,11 @@ class _Lowerer:
         elif padding == "VALID":
             Ho, Wo = (H - R) // sh + 1, (W - S) // sw + 1
             pads = (0, 0, 0, 0)
+        elif padding == "EXPLICIT":
+            ep = _attr_ints(nd, "explicit_paddings")
+            pads = (ep[2], ep[3], ep[4], ep[5])
+            Ho = (H + pads[0] + pads[1] - R) // sh + 1
+            Wo = (W + pads[2] + pads[3] - S) // sw + 1
         else:
             raise PlanError(f"depthwise padding {padding}")
 
@@ -765,36 +777,39 @@ class _Lowerer:
         if bn is not None:
             scale, offset, mean, var, eps = bn
             g_ = scale / np.sqrt(var + eps)
-            w = w * g_.reshape(1, 1, Cin, 1)
-            base = bias if bias is not None else np.zeros(Cin, np.float32)
+            w = w * g_.reshape(1, 1, Cin, M)
+            base = bias if bias is not None else np.zeros(K, np.float32)
             bias = (base - mean) * g_ + offset
         if bias is None:
-            bias = np.zeros(Cin, np.float32)
-        w_id = self.new_tensor((R, S, Cin), "f32", "weight",
+            bias = np.zeros(K, np.float32)
+        w_id = self.new_tensor((R, S, K), "f32", "weight",
                                f"{nd.name}/fused_w",
-                               weight=w.reshape(R, S, Cin))
-        b_id = self.new_tensor((Cin,), "f32", "weight",
+                               weight=w.reshape(R, S, K))
+        b_id = self.new_tensor((K,), "f32", "weight",
                                f"{nd.name}/fused_b", weight=bias)
         out_name = f"{final.name}:0"
         dw_act = act if residual is None else ACT_NONE
-        y = self.new_tensor((B, Ho, Wo, Cin), "f32", "activation",
+        y = self.new_tensor((B, Ho, Wo, K), "f32", "activation",
                             out_name if residual is None
                             else f"{nd.name}/dw:0")
+        params = {"stride": (sh, sw), "pads": pads,
+                  "act": dw_act, "rsc": (R, S, Cin),
+                  "hw": (H, W), "out_hw": (Ho, Wo)}
+        if M > 1:
+            params["mult"] = M
         self.ops.append(PlanOp("depthwise_conv", [x, w_id, b_id], [y],
-                               {"stride": (sh, sw), "pads": pads,
-                                "act": dw_act, "rsc": (R, S, Cin),
-                                "hw": (H, W), "out_hw": (Ho, Wo)}))
+                               params))
         if residual is not None:
             # rare shape (MobileNet residuals connect 1x1 convs): emit
             # the absorbed add/act as separate eltwise ops
-            y2 = self.new_tensor((B, Ho, Wo, Cin), "f32", "activation",
+            y2 = self.new_tensor((B, Ho, Wo, K), "f32", "activation",
                                  out_name if act == ACT_NONE
                                  else f"{nd.name}/res:0")
             self.ops.append(PlanOp("eltwise", [y, self.tid(residual)],
                                    [y2], {"fn": "add"}))
             y = y2
             if act != ACT_NONE:
-                y3 = self.new_tensor((B, Ho, Wo, Cin), "f32",
+                y3 = self.new_tensor((B, Ho, Wo, K), "f32",
                                      "activation", out_name)
                 self.ops.append(PlanOp("eltwise", [y], [y3], {"fn": act}))
                 y = y3

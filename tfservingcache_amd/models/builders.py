@@ -360,6 +360,100 @@ def build_mobilenet_v2(image_size=224, num_classes=1000, seed=0,
 
 
 # ---------------------------------------------------------------------------
+# Separable CNN (inference): DepthwiseConv2dNative with a channel
+# multiplier (Keras DepthwiseConv2D / SeparableConv2D(depth_multiplier=))
+# + BN + Relu6, then a 1x1 Conv2D + BN, with an identity residual where
+# the shapes match. The depthwise filter is [k,k,C,M]; output channel
+# c*M + m reads input channel c.
+# ---------------------------------------------------------------------------
+def build_separable_cnn(image_size=32, num_classes=10, depth_multiplier=2,
+                        seed=0):
+    """Stem 3x3/2 to 16 channels, then four separable blocks
+    (kernel, stride, M, out channels), d = depth_multiplier:
+    (3, 1, d, 16) + residual, (3, 2, 2d, 24), (5, 1, 3, 24) + residual,
+    (3, 2, 4d, 32); global mean, FC, softmax. With the default d = 2 the
+    multipliers 2, 4, 3, 8 reach every path of the depthwise kernel
+    (M = 3 is the scalar one)."""
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+    d = int(depth_multiplier)
+    if d < 1:
+        raise ValueError("depth_multiplier must be >= 1")
+
+    def bn(name, x, c, relu6):
+        scale = gb.const(f"{name}/gamma",
+                         np.abs(rng.standard_normal(c)).astype(np.float32)
+                         * 0.5 + 0.5)
+        offset = gb.const(f"{name}/beta",
+                          (rng.standard_normal(c) * 0.1).astype(np.float32))
+        mean = gb.const(f"{name}/mean",
+                        (rng.standard_normal(c) * 0.1).astype(np.float32))
+        var = gb.const(f"{name}/var",
+                       np.abs(rng.standard_normal(c)).astype(np.float32)
+                       * 0.5 + 0.5)
+        h = gb.node("FusedBatchNormV3", f"{name}/bn",
+                    [x, scale, offset, mean, var], T=f32, U=f32,
+                    epsilon=gb.a_float(1e-3),
+                    is_training=gb.a_bool(False),
+                    data_format=gb.a_str("NHWC"))
+        if relu6:
+            h = gb.node("Relu6", f"{name}/relu6", [h], T=f32)
+        return h
+
+    def conv(name, x, cin, cout, k, stride, relu):
+        w = gb.const(f"{name}/w", (rng.standard_normal((k, k, cin, cout))
+                                   * np.sqrt(2.0 / (k * k * cin))
+                                   ).astype(np.float32))
+        c = gb.node("Conv2D", f"{name}/conv", [x, w], T=f32,
+                    strides=gb.a_ints([1, stride, stride, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NHWC"))
+        h = bn(name, c, cout, relu6=False)
+        if relu:
+            h = gb.node("Relu", f"{name}/relu", [h], T=f32)
+        return h
+
+    def dwise(name, x, c, k, stride, m):
+        w = gb.const(f"{name}/dw", (rng.standard_normal((k, k, c, m))
+                                    * np.sqrt(2.0 / (k * k))
+                                    ).astype(np.float32))
+        h = gb.node("DepthwiseConv2dNative", f"{name}/depthwise", [x, w],
+                    T=f32, strides=gb.a_ints([1, stride, stride, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NHWC"))
+        return bn(name, h, c * m, relu6=True)
+
+    x = gb.placeholder("input", np.float32,
+                       [-1, image_size, image_size, 3],
+                       signature_name="input")
+    cin = 16
+    h = conv("stem", x, 3, cin, 3, 2, relu=True)
+    cfg = [(3, 1, d, 16), (3, 2, 2 * d, 24), (5, 1, 3, 24),
+           (3, 2, 4 * d, 32)]
+    for bi, (k, stride, m, cout) in enumerate(cfg):
+        name = f"block{bi}"
+        inp = h
+        h = dwise(f"{name}/dw", h, cin, k, stride, m)
+        h = conv(f"{name}/pw", h, cin * m, cout, 1, 1, relu=False)
+        if stride == 1 and cin == cout:
+            h = gb.node("AddV2", f"{name}/add", [h, inp], T=f32)
+        cin = cout
+    gap_axes = gb.const("gap/axes", np.array([1, 2], dtype=np.int32))
+    pooled = gb.node("Mean", "gap", [h, gap_axes], T=f32,
+                     keep_dims=gb.a_bool(False))
+    wfc = gb.const("fc/w", (rng.standard_normal((cin, num_classes))
+                            * np.sqrt(1.0 / cin)).astype(np.float32))
+    bfc = gb.const("fc/b", np.zeros(num_classes, dtype=np.float32))
+    logits = gb.node("MatMul", "fc/mm", [pooled, wfc], T=f32)
+    logits = gb.node("BiasAdd", "logits", [logits, bfc], T=f32)
+    probs = gb.node("Softmax", "probs", [logits], T=f32)
+    gb.mark_output("probs", probs)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # U-Net (inference): two-level encoder-decoder with skip connections —
 # the upsampling model family (segmentation heads, FPN necks,
 # autoencoder decoders). conv+BN+ReLU throughout; the decoder upsamples
