@@ -38,6 +38,8 @@ void launch_bn_act(hipStream_t s, const ushort* x, const ushort* scale,
                    int act);
 void launch_softmax(hipStream_t s, const ushort* x, ushort* y,
                     int64_t rows, int64_t cols);
+// y = (x - mean) * rsqrt(var + eps) * gamma + beta over the last dim, with
+// var = mean((x - mean)^2) taken in a second pass over the row
 void launch_layernorm(hipStream_t s, const ushort* x, const ushort* gamma,
                       const ushort* beta, ushort* y, int64_t rows,
                       int64_t cols, float eps);
@@ -72,7 +74,7 @@ void launch_f32_to_bf16(hipStream_t s, const float* x, ushort* y,
 void launch_cast(hipStream_t s, const void* x, void* y, int64_t n,
                  int mode);
 // rowwise argmax over the last dim: [rows, cols] bf16 -> i32 (first
-// max wins on ties, TF semantics)
+// max wins on ties, TF semantics; a row of all -inf answers 0)
 void launch_argmax_last(hipStream_t s, const ushort* x, int* y,
                         int64_t rows, int64_t cols);
 void launch_bf16_to_f32(hipStream_t s, const ushort* x, float* y,

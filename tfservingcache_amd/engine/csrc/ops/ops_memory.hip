@@ -6,6 +6,7 @@
 // grid-stride (G11), accumulation is f32.
 #include "../common.h"
 #include "../kernels.h"
+#include "../transpose_gate.h"
 
 #include <stdexcept>
 #include <string>
@@ -201,10 +202,10 @@ __global__ void k_softmax(const ushort* __restrict__ x,
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const ushort* xr = x + row * cols;
     ushort* yr = y + row * cols;
-    float mx = -3.0e38f;
+    float mx = -INFINITY;
     for (int64_t i = threadIdx.x; i < cols; i += TPB)
       mx = fmaxf(mx, bf2f(xr[i]));
-    mx = block_reduce(mx, MaxOp(), -3.0e38f);
+    mx = block_reduce(mx, MaxOp(), -INFINITY);
     float sum = 0.f;
     for (int64_t i = threadIdx.x; i < cols; i += TPB)
       sum += __expf(bf2f(xr[i]) - mx);
@@ -231,11 +232,11 @@ __global__ void k_softmax_wave(const ushort* __restrict__ x,
     ushort* yr = y + row * cols;
     float v[VPL];
     int n = (cols + WAVE - 1) / WAVE;   // elements this lane handles
-    float mx = -3.0e38f;
+    float mx = -INFINITY;
     #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       int i = j * WAVE + lane;
-      v[j] = (j < n && i < cols) ? bf2f(xr[i]) : -3.0e38f;
+      v[j] = (j < n && i < cols) ? bf2f(xr[i]) : -INFINITY;
       mx = fmaxf(mx, v[j]);
     }
     #pragma unroll
@@ -278,7 +279,10 @@ void launch_softmax(hipStream_t s, const ushort* x, ushort* y,
 }
 
 // ---------------------------------------------------------------------------
-// layernorm (last dim): one block per row
+// layernorm (last dim): one block per row. Two passes for the statistics:
+// the mean, then the mean of squared deviations from it (E[x^2] - mean^2
+// cancels in f32 on rows whose mean is large against their spread); the
+// second and third reads of the row hit the cache.
 // ---------------------------------------------------------------------------
 __global__ void k_layernorm(const ushort* __restrict__ x,
                             const ushort* __restrict__ gamma,
@@ -288,17 +292,17 @@ __global__ void k_layernorm(const ushort* __restrict__ x,
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const ushort* xr = x + row * cols;
     ushort* yr = y + row * cols;
-    float sum = 0.f, sq = 0.f;
+    float sum = 0.f;
+    for (int64_t i = threadIdx.x; i < cols; i += TPB)
+      sum += bf2f(xr[i]);
+    float mean = block_reduce(sum, SumOp(), 0.f) / cols;
+    float sq = 0.f;
     for (int64_t i = threadIdx.x; i < cols; i += TPB) {
-      float v = bf2f(xr[i]);
-      sum += v;
-      sq += v * v;
+      float d = bf2f(xr[i]) - mean;
+      sq += d * d;
     }
-    sum = block_reduce(sum, SumOp(), 0.f);
-    sq = block_reduce(sq, SumOp(), 0.f);
-    float mean = sum / cols;
-    float var = sq / cols - mean * mean;
-    float rstd = rsqrtf(var > 0.f ? var + eps : eps);
+    float var = block_reduce(sq, SumOp(), 0.f) / cols;   // >= 0
+    float rstd = rsqrtf(var + eps);
     for (int64_t i = threadIdx.x; i < cols; i += TPB) {
       float v = (bf2f(xr[i]) - mean) * rstd;
       yr[i] = f2bf(v * bf2f(gamma[i]) + bf2f(beta[i]));
@@ -375,7 +379,7 @@ __global__ void k_pool(const ushort* __restrict__ x, ushort* __restrict__ y,
     int64_t t = i / C;
     int wo = int(t % Wo); t /= Wo;
     int ho = int(t % Ho); int n = int(t / Ho);
-    float acc = is_max ? -3.0e38f : 0.f;
+    float acc = is_max ? -INFINITY : 0.f;
     int count = 0;
     for (int r = 0; r < kh; ++r) {
       int hi = ho * sh + r - pt;
@@ -410,7 +414,7 @@ __global__ void k_pool_v8(const ushort* __restrict__ x,
     int ho = int(t % Ho); int n = int(t / Ho);
     float acc[8];
     #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = is_max ? -3.0e38f : 0.f;
+    for (int j = 0; j < 8; ++j) acc[j] = is_max ? -INFINITY : 0.f;
     int count = 0;
     for (int r = 0; r < kh; ++r) {
       int hi = ho * sh + r - pt;
@@ -496,7 +500,9 @@ __global__ void k_transpose(const ushort* __restrict__ x,
 
 // fast path: the permutation keeps the LAST dim innermost (e.g. the
 // attention head split/merge perm [0,2,1,3]) and it is a multiple of 8
-// bf16 — move 16-byte chunks instead of scalars
+// bf16 — move 16-byte chunks instead of scalars. transpose_takes_v8
+// (transpose_gate.h) decides; it also looks at the pointers and the outer
+// strides, since strided_copy comes through here with an offset source.
 __global__ void k_transpose_v8(const ushort* __restrict__ x,
                                ushort* __restrict__ y, TransArgs ta,
                                int64_t n_grp, int last) {
@@ -529,7 +535,7 @@ void launch_transpose(hipStream_t s, const ushort* x, ushort* y, int ndim,
     ta.in_strides[d] = d < ndim ? in_strides[d] : 0;
   }
   int last = ndim > 0 ? int(out_dims[ndim - 1]) : 0;
-  if (ndim >= 2 && in_strides[ndim - 1] == 1 && last % 8 == 0) {
+  if (transpose_takes_v8(x, y, ndim, out_dims, in_strides)) {
     int64_t n_grp = n_out / 8;
     hipLaunchKernelGGL(k_transpose_v8, dim3(grid_for(n_grp)), dim3(TPB),
                        0, s, x, y, ta, n_grp, last);
@@ -969,7 +975,8 @@ void launch_cast(hipStream_t s, const void* x, void* y, int64_t n,
                        reinterpret_cast<int*>(y), n);
 }
 
-// one wave per row; first-max-wins tie-breaking via (value, -index)
+// one wave per row; first-max-wins: strict > within a lane, (value, lower
+// index) across lanes
 __global__ __launch_bounds__(256)
 void k_argmax_last(const ushort* __restrict__ x, int* __restrict__ y,
                    int64_t rows, int64_t cols) {
@@ -979,11 +986,14 @@ void k_argmax_last(const ushort* __restrict__ x, int* __restrict__ y,
   for (int64_t row = (int64_t)blockIdx.x * (256 / WAVE) + wv;
        row < rows; row += waves_total) {
     const ushort* xr = x + row * cols;
-    float best = -3.0e38f;
-    int besti = 0x7FFFFFFF;
+    // seeded with (-inf, 0): a row with nothing above -inf answers 0,
+    // as TF does, and a lane past the row's end loses every comparison
+    // against a real element except an equal -inf, where 0 is right
+    float best = -INFINITY;
+    int besti = 0;
     for (int64_t i = lane; i < cols; i += WAVE) {
       float v = bf2f(xr[i]);
-      if (v > best || (v == best && int(i) < besti)) {
+      if (v > best) {              // i ascends within a lane: first wins
         best = v;
         besti = int(i);
       }
