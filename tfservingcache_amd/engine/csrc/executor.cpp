@@ -191,8 +191,19 @@ static void launch_call(const Call& c, hipStream_t s) {
                   reinterpret_cast<void*>(c.ptrs[1]), I[0], int(I[1]));
       break;
     case K_ARGMAX_LAST:
-      launch_argmax_last(s, cp(0), reinterpret_cast<int*>(c.ptrs[1]),
-                         I[0], I[1]);
+      // ptrs: [x, idx]; ints: [rows, cols] is argmax. The top-k form is
+      // ptrs: [x, idx, vals, scratch|0]; ints: [rows, cols, k, P]
+      if (I.size() == 2 && c.ptrs.size() == 2) {
+        launch_argmax_last(s, cp(0), reinterpret_cast<int*>(c.ptrs[1]),
+                           I[0], I[1]);
+      } else if (I.size() == 4 && c.ptrs.size() == 4) {
+        launch_topk_last(s, cp(0), reinterpret_cast<int*>(c.ptrs[1]), p(2),
+                         reinterpret_cast<void*>(c.ptrs[3]), I[0], I[1],
+                         I[2], I[3]);
+      } else {
+        throw std::runtime_error(
+            "argmax_last takes 2 ptrs and 2 ints, top-k 4 and 4");
+      }
       break;
     case K_DEPTHWISE:
       // ptrs: [x, w, bias, y]
@@ -447,6 +458,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
              const std::vector<uintptr_t>& bases) {
             return std::unique_ptr<ExecPlan>(t.instantiate(ws, bases));
           });
+
+  mod.def("topk_sort_max_cols", &tfsc::topk_sort_max_cols);
+  mod.def("set_topk_sort_max_cols", &tfsc::set_topk_sort_max_cols);
 
   register_fastpath(mod);
   register_frontend(mod);

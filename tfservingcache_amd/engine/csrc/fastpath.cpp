@@ -383,6 +383,13 @@ class FastModel {
       wanted.push_back(&io);
     }
     for (auto* io : wanted) {
+      if (io->is_int) {               // i32 output (ArgMax / TopKV2 ids)
+        HIPCHK(hipMemcpyAsync(reinterpret_cast<void*>(io->pin),
+                              reinterpret_cast<void*>(io->dev),
+                              size_t(total) * io->row_elems * 4,
+                              hipMemcpyDeviceToHost, s));
+        continue;
+      }
       launch_bf16_to_f32(s, reinterpret_cast<const ushort*>(io->dev),
                          reinterpret_cast<float*>(io->dev_stage),
                          total * io->row_elems);
@@ -413,7 +420,7 @@ class FastModel {
       for (auto* io : wanted) {
         std::string tp;
         w_tag(tp, 1, 0);
-        w_varint(tp, 1);
+        w_varint(tp, io->is_int ? 3 : 1);      // DT_INT32 / DT_FLOAT
         {
           std::string shape;
           {

@@ -77,6 +77,23 @@ void launch_cast(hipStream_t s, const void* x, void* y, int64_t n,
 // max wins on ties, TF semantics; a row of all -inf answers 0)
 void launch_argmax_last(hipStream_t s, const ushort* x, int* y,
                         int64_t rows, int64_t cols);
+// rowwise top-k over the last dim (TF TopKV2), ops/topk.hip:
+// [rows, cols] bf16 -> vals [rows, k] bf16 (the elements' own bits) and
+// idx [rows, k] i32, values descending, equal values by lower index
+// (+0.0 and -0.0 are equal). Exact selection, no arithmetic. P > 1
+// splits every row into P segments of ceil(cols / P) columns whose
+// partial results meet in `scratch` (rows * P * k * 8 bytes, 8-byte
+// aligned; may be null when P == 1) and a second launch picks the final
+// k. NaN order is unspecified. Throws before any launch unless
+// 1 <= k <= min(cols, 1024), 1 <= P <= min(cols, 4096), cols < 2^31 and
+// scratch is set when P > 1.
+void launch_topk_last(hipStream_t s, const ushort* x, int* idx, ushort* vals,
+                      void* scratch, int64_t rows, int64_t cols, int64_t k,
+                      int64_t P);
+// rows of at most this many columns (<= 2048) are sorted whole instead of
+// radix-selected; a measurement switch (scripts/topk_probe.py)
+int topk_sort_max_cols();
+void set_topk_sort_max_cols(int cols);
 void launch_bf16_to_f32(hipStream_t s, const ushort* x, float* y,
                         int64_t n);
 

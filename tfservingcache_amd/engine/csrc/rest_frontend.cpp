@@ -89,18 +89,22 @@ static void write_float(std::string& out, float v) {
   out.append(buf, size_t(n));
 }
 
-// write values[off .. off+prod(dims[d:])) as nested arrays
-static void write_nested(std::string& out, const float* vals,
+// write values[off .. off+prod(dims[d:])) as nested arrays; the words
+// are f32, or i32 when is_int (a DT_INT32 output)
+static void write_nested(std::string& out, const float* vals, bool is_int,
                          const std::vector<int64_t>& dims, size_t d,
                          size_t& off) {
   if (d == dims.size()) {
-    write_float(out, vals[off++]);
+    if (is_int)
+      out += std::to_string(reinterpret_cast<const int32_t*>(vals)[off++]);
+    else
+      write_float(out, vals[off++]);
     return;
   }
   out.push_back('[');
   for (int64_t i = 0; i < dims[d]; ++i) {
     if (i) out.push_back(',');
-    write_nested(out, vals, dims, d + 1, off);
+    write_nested(out, vals, is_int, dims, d + 1, off);
   }
   out.push_back(']');
 }
@@ -573,6 +577,7 @@ class RestFrontend {
       if (outs.size() == 1) {
         size_t off = 0;
         write_nested(*out, reinterpret_cast<const float*>(outs[0].data),
+                     outs[0].is_int,
                      outs[0].dims, 0, off);
       } else {
         out->push_back('{');
@@ -583,6 +588,7 @@ class RestFrontend {
           out->append("\": ");
           size_t off = 0;
           write_nested(*out, reinterpret_cast<const float*>(outs[i].data),
+                       outs[i].is_int,
                        outs[i].dims, 0, off);
         }
         out->push_back('}');
@@ -595,6 +601,7 @@ class RestFrontend {
     if (outs.size() == 1) {
       size_t off = 0;
       write_nested(*out, reinterpret_cast<const float*>(outs[0].data),
+                   outs[0].is_int,
                    outs[0].dims, 0, off);
     } else {
       int64_t rows = outs[0].dims.empty() ? 0 : outs[0].dims[0];
@@ -612,6 +619,7 @@ class RestFrontend {
                                     outs[i].dims.end());
           write_nested(*out,
                        reinterpret_cast<const float*>(outs[i].data),
+                       outs[i].is_int,
                        tail, 0, offs[i]);
         }
         out->push_back('}');

@@ -72,8 +72,9 @@ struct PReader {
 struct OutTensor {
   std::string alias;
   std::vector<int64_t> dims;     // includes batch dim
-  const uint8_t* data = nullptr; // f32 tensor_content
+  const uint8_t* data = nullptr; // f32 (or i32) tensor_content
   size_t nbytes = 0;
+  bool is_int = false;           // DT_INT32 instead of DT_FLOAT
 };
 
 // parse PredictResponse: outputs map (field 1) of TensorProto with
@@ -125,6 +126,8 @@ static std::vector<OutTensor> parse_response(const std::string& body) {
                   rs.skip(int(stag & 7));
                 }
               }
+            } else if (tf == 1 && tw == 0) {     // dtype
+              t.is_int = rt.varint() == 3;       // DT_INT32
             } else if (tf == 4 && tw == 2) {     // tensor_content
               uint64_t cn = rt.need(rt.varint());
               t.data = rt.p;

@@ -70,6 +70,26 @@ def _pad256b(n: int) -> int:
     return (n + 255) // 256 * 256
 
 
+def topk_segments(rows: int, cols: int, k: int) -> int:
+    """P, the number of segments a top-k call splits every row into
+    (csrc/ops/topk.hip: one workgroup per segment, then a merge launch
+    over the P*k partial results). One workgroup walks its segment
+    serially, so a long row on few workgroups leaves the chip idle; the
+    merge reads P*k composites, so P grows as sqrt(cols / k).
+
+    Every limit is the edge of what profiles/topk.md measured, and inside
+    them the split won every time: rows of at least 16384 columns,
+    k <= 100, segments of at least 2048 columns, at most 256 segments a
+    row and rows * P <= 256 (the chip's CUs). Outside them P = 1."""
+    if cols < 16384 or k > 100:
+        return 1
+    P = min(int((cols / k) ** 0.5), cols // 2048, 256 // max(rows, 1), 256)
+    if P < 2:
+        return 1
+    seglen = -(-cols // P)
+    return -(-cols // seglen)           # no empty last segment
+
+
 def _numel(shape) -> int:
     return int(np.prod(shape)) if shape else 1
 
@@ -221,6 +241,13 @@ class _Emitter:
                     H, W = op.params["hw"]
                     c8 = (Cin + 7) // 8 * 8
                     scratch_sizes[oi] = self.batch * H * W * c8 * 2
+            if op.kind == "topk_last":
+                # a split row's partial results: P lists of k 64-bit
+                # composites per row
+                rows, cols = _rows_cols(self.shapes[op.inputs[0]])
+                P = topk_segments(rows, cols, op.params["k"])
+                if P > 1:
+                    scratch_sizes[oi] = rows * P * op.params["k"] * 8
 
         self.bufs: Dict[int, _BufInfo] = {}
         self.scratch_off: Dict[int, int] = {}
@@ -344,6 +371,17 @@ class _Emitter:
                 call("DEPTHWISE", io(op, 3), ints)
             elif k in _ROWWISE:
                 call(_ROWWISE[k], io(op, 1), _rows_cols(xs))
+            elif k == "topk_last":
+                # ARGMAX_LAST's 4-pointer / 4-int form (argmax is top-1
+                # without values): [x, idx, vals, scratch|null],
+                # [rows, cols, k, P]
+                rows, cols = _rows_cols(xs)
+                P = topk_segments(rows, cols, p["k"])
+                call("ARGMAX_LAST",
+                     [self._ptr(op.inputs[0]), self._ptr(op.outputs[1]),
+                      self._ptr(op.outputs[0]),
+                      self._scratch(oi) if P > 1 else None],
+                     [rows, cols, p["k"], P])
             elif k == "layernorm":
                 call("LAYERNORM", io(op, 3), _rows_cols(xs),
                      [float(p["eps"])])

@@ -275,6 +275,13 @@ class CpuExecutor:
         elif k == "argmax_last":
             x = _get(op.inputs[0])
             vals[op.outputs[0]] = x.argmax(axis=-1).astype(np.int32)
+        elif k == "topk_last":
+            # TF TopKV2: values descending, equal values by lower index
+            # (-0.0 == +0.0); the stable sort of -x is that order
+            x = _get(op.inputs[0])
+            idx = np.argsort(-x, axis=-1, kind="stable")[..., :p["k"]]
+            vals[op.outputs[0]] = np.take_along_axis(x, idx, axis=-1)
+            vals[op.outputs[1]] = idx.astype(np.int32)
         elif k == "resize":
             vals[op.outputs[0]] = _resize(
                 _get(op.inputs[0]), p["out_hw"], p["mode"],

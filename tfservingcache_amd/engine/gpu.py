@@ -1109,19 +1109,24 @@ class GpuModel:
         outs = []
         for alias, idx in plan.sig_outputs.items():
             v = ctx.view(idx)
-            if v.dtype != torch.bfloat16:
-                ctx.fast_id = -1     # non-bf16 output: python path only
-                return
             rows = v.shape[0] if v.ndim else 1
             row_elems = int(np.prod(v.shape[1:])) if v.ndim > 1 else 1
             raw = pinned_pool.alloc(torch, rows * row_elems * 4)
             ctx._pin_raws.append(raw)
-            pin = _pin_view(torch, raw, (rows, row_elems), torch.float32)
-            stage = torch.empty((rows, row_elems), dtype=torch.float32,
-                                device=self.device)
-            keep.extend([pin, stage])
-            outs.append(ext.FastIO(alias, False, pin.data_ptr(),
-                                   stage.data_ptr(), v.data_ptr(),
+            # an i32 output (ArgMax, TopKV2 indices) is copied out as it
+            # is; a bf16 one goes through an f32 staging buffer
+            is_int = v.dtype == torch.int32
+            pin = _pin_view(torch, raw, (rows, row_elems),
+                            torch.int32 if is_int else torch.float32)
+            stage_ptr = 0
+            if not is_int:
+                stage = torch.empty((rows, row_elems), dtype=torch.float32,
+                                    device=self.device)
+                keep.append(stage)
+                stage_ptr = stage.data_ptr()
+            keep.append(pin)
+            outs.append(ext.FastIO(alias, bool(is_int), pin.data_ptr(),
+                                   stage_ptr, v.data_ptr(),
                                    row_elems, [int(d) for d in v.shape[1:]]))
         ctx._fast_keep = keep
         ctx.fast_id = self._fast.add_context(

@@ -398,6 +398,9 @@ class _Lowerer:
         if op == "ArgMax":
             self.lower_argmax(nd, out)
             return
+        if op in ("TopKV2", "TopK"):
+            self.lower_topk(nd)
+            return
         if op == "MatMul":
             self.lower_matmul(nd, out)
             return
@@ -1186,6 +1189,39 @@ class _Lowerer:
             raise PlanError("ArgMax only over the last axis")
         y = self.new_tensor(tuple(xs[:-1]), "i32", "activation", out)
         self.ops.append(PlanOp("argmax_last", [x], [y], {}))
+
+    # largest k one workgroup's LDS candidate array holds (csrc/ops/topk.hip)
+    TOPK_MAX_K = 1024
+
+    def lower_topk(self, nd: g.NodeDef) -> None:
+        """TopKV2 (k is the second input) / TopK (k is an attribute) over
+        the last axis -> one `topk_last` op with two outputs: `name:0`
+        values f32 [..., k], descending, equal values by lower index,
+        and `name:1` indices [..., k]. sorted=false is served sorted (TF
+        leaves that order open); index_type int64 yields the engine's
+        i32 like ArgMax's output_type."""
+        x = self.tid(nd.input[0])
+        xt = self.tensors[x]
+        if xt.dtype != "f32":
+            raise PlanError(f"{nd.op} {nd.name}: only f32 input supported")
+        if nd.op == "TopK":
+            k = int(_attr_i(nd, "k", 0))
+        else:
+            kv = self.const_value(nd.input[1]) if len(nd.input) > 1 else None
+            if kv is None or np.asarray(kv).size != 1:
+                raise PlanError(f"{nd.op} {nd.name}: k must be a constant")
+            k = int(np.asarray(kv).reshape(-1)[0])
+        if not xt.shape or is_sym(xt.shape[-1]):
+            raise PlanError(f"{nd.op} {nd.name}: the last axis must be "
+                            f"concrete (input shape {xt.shape})")
+        cols = int(xt.shape[-1])
+        if k < 1 or k > cols or k > self.TOPK_MAX_K:
+            raise PlanError(f"{nd.op} {nd.name}: k = {k} outside "
+                            f"[1, min({cols}, {self.TOPK_MAX_K})]")
+        shape = tuple(xt.shape[:-1]) + (k,)
+        vals = self.new_tensor(shape, "f32", "activation", f"{nd.name}:0")
+        idx = self.new_tensor(shape, "i32", "activation", f"{nd.name}:1")
+        self.ops.append(PlanOp("topk_last", [x], [vals, idx], {"k": k}))
 
     def lower_einsum(self, nd: g.NodeDef, out: str) -> None:
         """Einsum (transformer SavedModel exports). Supported family:

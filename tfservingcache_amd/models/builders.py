@@ -454,6 +454,47 @@ def build_separable_cnn(image_size=32, num_classes=10, depth_multiplier=2,
 
 
 # ---------------------------------------------------------------------------
+# Two-tower retrieval (brute-force index): a query MLP, the scores of the
+# query embedding against a constant candidate matrix, and tf.math.top_k
+# over them. TopKV2's outputs are `top_k:0` (values) and `top_k:1`
+# (indices).
+# ---------------------------------------------------------------------------
+def build_retrieval(d_query=32, d_hidden=64, d_embed=32, n_items=3001,
+                    k=10, seed=0):
+    """relu(x W1 + b1) W2 + b2 -> MatMul with candidates [d_embed, n_items]
+    -> TopKV2(k). Signature outputs: `scores` [B, k], `ids` [B, k] (i32)
+    and `logits` [B, n_items], the scores the selection ran on."""
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+    i32 = gb.a_type(3)
+
+    def dense(name, x, din, dout, relu):
+        w = gb.const(f"{name}/w", (rng.standard_normal((din, dout))
+                                   * np.sqrt(1.0 / din)).astype(np.float32))
+        b = gb.const(f"{name}/b",
+                     (rng.standard_normal(dout) * 0.1).astype(np.float32))
+        h = gb.node("MatMul", f"{name}/mm", [x, w], T=f32)
+        h = gb.node("BiasAdd", f"{name}/bias", [h, b], T=f32)
+        return gb.node("Relu", f"{name}/relu", [h], T=f32) if relu else h
+
+    x = gb.placeholder("query", np.float32, [-1, d_query],
+                       signature_name="query")
+    h = dense("tower/fc1", x, d_query, d_hidden, relu=True)
+    h = dense("tower/fc2", h, d_hidden, d_embed, relu=False)
+    cand = gb.const("candidates", (rng.standard_normal((d_embed, n_items))
+                                   * np.sqrt(1.0 / d_embed)
+                                   ).astype(np.float32))
+    logits = gb.node("MatMul", "logits", [h, cand], T=f32)
+    top = gb.node("TopKV2", "top_k", [logits, gb.const("k", np.int32(k))],
+                  T=f32, sorted=gb.a_bool(True), index_type=i32)
+    gb.mark_output("scores", f"{top}:0")
+    gb.mark_output("ids", f"{top}:1")
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # U-Net (inference): two-level encoder-decoder with skip connections —
 # the upsampling model family (segmentation heads, FPN necks,
 # autoencoder decoders). conv+BN+ReLU throughout; the decoder upsamples
