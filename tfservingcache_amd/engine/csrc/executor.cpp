@@ -88,10 +88,30 @@ static void launch_call(const Call& c, hipStream_t s) {
                        c.floats[0]);
       break;
     case K_MEAN_LAST:
-      launch_reduce_mean_last(s, cp(0), p(1), I[0], I[1]);
+      // ptrs: [x, y]; ints: [rows, cols] is the mean. The reduce form is
+      // ptrs: [x, y, scratch|0]; ints: [rows, cols, fn, P]
+      if (I.size() == 2 && c.ptrs.size() == 2) {
+        launch_reduce_mean_last(s, cp(0), p(1), I[0], I[1]);
+      } else if (I.size() == 4 && c.ptrs.size() == 3) {
+        launch_reduce(s, cp(0), p(1), reinterpret_cast<void*>(c.ptrs[2]),
+                      I[0], I[1], 1, int(I[2]), I[3]);
+      } else {
+        throw std::runtime_error(
+            "mean_last takes 2 ptrs and 2 ints, reduce 3 and 4");
+      }
       break;
     case K_MEAN_MID:
-      launch_reduce_mean_mid(s, cp(0), p(1), I[0], I[1], I[2]);
+      // ptrs: [x, y]; ints: [d0, d1, d2] is the mean. The reduce form is
+      // ptrs: [x, y, scratch|0]; ints: [d0, d1, d2, fn, P]
+      if (I.size() == 3 && c.ptrs.size() == 2) {
+        launch_reduce_mean_mid(s, cp(0), p(1), I[0], I[1], I[2]);
+      } else if (I.size() == 5 && c.ptrs.size() == 3) {
+        launch_reduce(s, cp(0), p(1), reinterpret_cast<void*>(c.ptrs[2]),
+                      I[0], I[1], I[2], int(I[3]), I[4]);
+      } else {
+        throw std::runtime_error(
+            "mean_mid takes 2 ptrs and 3 ints, reduce 3 and 5");
+      }
       break;
     case K_POOL:
       launch_pool(s, cp(0), p(1), I[0] != 0, int(I[1]), int(I[2]),
@@ -461,6 +481,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
 
   mod.def("topk_sort_max_cols", &tfsc::topk_sort_max_cols);
   mod.def("set_topk_sort_max_cols", &tfsc::set_topk_sort_max_cols);
+  mod.def("reduce_wave_max_cols", &tfsc::reduce_wave_max_cols);
+  mod.def("reduce_cols_tx_max", &tfsc::reduce_cols_tx_max);
+  mod.def("reduce_cols_wg_target", &tfsc::reduce_cols_wg_target);
+  mod.def("set_reduce_thresholds", &tfsc::set_reduce_thresholds);
 
   register_fastpath(mod);
   register_frontend(mod);

@@ -94,6 +94,29 @@ void launch_topk_last(hipStream_t s, const ushort* x, int* idx, ushort* vals,
 // radix-selected; a measurement switch (scripts/topk_probe.py)
 int topk_sort_max_cols();
 void set_topk_sort_max_cols(int cols);
+// reduction over the middle axis of a bf16 view [outer, red, inner]
+// (inner == 1: over the last axis), ops/reduce.hip: y [outer, inner]
+// bf16, f32 accumulation, one rounding. fn: 0 mean, 1 sum, 2 max, 3 min,
+// 4 prod. P > 1 splits red into P segments of ceil(red / P) whose f32
+// partials meet in `scratch` (outer * inner * P * 4 bytes; may be null
+// when P == 1) and a second launch folds them. Max and min skip NaN.
+// Throws before any launch unless every extent is >= 1,
+// 1 <= P <= min(red, 4096) and scratch is set when P > 1.
+void launch_reduce(hipStream_t s, const ushort* x, ushort* y, void* scratch,
+                   int64_t outer, int64_t red, int64_t inner, int fn,
+                   int64_t P);
+// rows of at most wave_max_cols columns run one wave per row, longer ones
+// one workgroup per (row, segment); a k_reduce_cols tile is at most
+// cols_tx_max lanes wide (a power of two <= 256) and narrows, down to 8
+// lanes, while the launch has fewer than cols_wg_target workgroups (0:
+// never); reduce_cols_lg_tx is log2 of the width chosen. Measurement
+// switches (scripts/reduce_probe.py).
+int reduce_wave_max_cols();
+int reduce_cols_tx_max();
+int reduce_cols_wg_target();
+int reduce_cols_lg_tx(int64_t outer, int64_t inner, int64_t P, bool vec);
+void set_reduce_thresholds(int wave_max_cols, int cols_tx_max,
+                           int cols_wg_target);
 void launch_bf16_to_f32(hipStream_t s, const ushort* x, float* y,
                         int64_t n);
 

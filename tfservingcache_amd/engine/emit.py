@@ -90,6 +90,47 @@ def topk_segments(rows: int, cols: int, k: int) -> int:
     return -(-cols // seglen)           # no empty last segment
 
 
+_REDUCE_CODE = {"mean": 0, "sum": 1, "max": 2, "min": 3, "prod": 4}
+
+# limits of reduce_segments, from profiles/reductions.md
+REDUCE_SPLIT_MIN_BYTES = 1 << 16     # least input of one unsplit workgroup
+REDUCE_SEG_MIN_BYTES = 1 << 13       # least input one segment reads
+REDUCE_MAX_WGS_ROWS = 1024           # inner == 1: four workgroups per CU
+REDUCE_MAX_WGS_COLS = 512            # inner > 1: two
+REDUCE_MAX_SEGMENTS = 512
+
+
+def reduce_segments(outer: int, red: int, inner: int) -> int:
+    """P, the number of segments a `reduce` call splits the reduced axis
+    of its [outer, red, inner] view into (csrc/ops/reduce.hip: one
+    workgroup per segment writes an f32 partial, a second launch folds
+    the P partials). Unsplit, the call runs `outer` workgroups when
+    inner == 1 and up to outer * ceil(inner / 64) otherwise (the column
+    kernel narrows its tile to 8 lanes of 8 channels when workgroups are
+    few), each walking its whole reduced axis with a few loads in
+    flight: a long axis on few workgroups leaves most of the 256 CUs
+    idle.
+
+    The split pays for a second launch, so it starts only where one
+    workgroup's input reaches REDUCE_SPLIT_MIN_BYTES, keeps every
+    segment at REDUCE_SEG_MIN_BYTES or more, and stops at
+    REDUCE_MAX_WGS_* workgroups and REDUCE_MAX_SEGMENTS. Every limit is
+    where the gain ended, or the edge of what was measured, in
+    profiles/reductions.md."""
+    tile = 1 if inner == 1 else min(inner, 64)
+    wgs = outer * -(-inner // tile)
+    wg_bytes = red * tile * 2
+    if wg_bytes < REDUCE_SPLIT_MIN_BYTES:
+        return 1
+    max_wgs = REDUCE_MAX_WGS_ROWS if inner == 1 else REDUCE_MAX_WGS_COLS
+    P = min(wg_bytes // REDUCE_SEG_MIN_BYTES, max_wgs // max(wgs, 1),
+            REDUCE_MAX_SEGMENTS, red)
+    if P < 2:
+        return 1
+    seglen = -(-red // P)
+    return -(-red // seglen)            # no empty last segment
+
+
 def _numel(shape) -> int:
     return int(np.prod(shape)) if shape else 1
 
@@ -248,6 +289,12 @@ class _Emitter:
                 P = topk_segments(rows, cols, op.params["k"])
                 if P > 1:
                     scratch_sizes[oi] = rows * P * op.params["k"] * 8
+            if op.kind == "reduce":
+                # a split axis's partials: P f32 per output element
+                outer, red, inner = self._reduce_view(op)
+                P = reduce_segments(outer, red, inner)
+                if P > 1:
+                    scratch_sizes[oi] = outer * inner * P * 4
 
         self.bufs: Dict[int, _BufInfo] = {}
         self.scratch_off: Dict[int, int] = {}
@@ -326,6 +373,14 @@ class _Emitter:
     def _scratch(self, oi: int):
         return (WS, self.scratch_off[oi])
 
+    def _reduce_view(self, op: PlanOp) -> Tuple[int, int, int]:
+        """A reduce op's [outer, red, inner] at this batch."""
+        view = self.plan.resolve_shape(op.params["view"], self.batch)
+        if _numel(view) != _numel(self.shapes[op.inputs[0]]):
+            raise RuntimeError(f"GPU reduce: view {view} does not cover "
+                               f"input {self.shapes[op.inputs[0]]}")
+        return view
+
     def _weight_shape(self, idx: int) -> Optional[Tuple[int, ...]]:
         """Shape of a constant weight operand, None for an activation."""
         if idx in self.layout.slots or idx in self.layout.int_idx:
@@ -382,6 +437,18 @@ class _Emitter:
                       self._ptr(op.outputs[0]),
                       self._scratch(oi) if P > 1 else None],
                      [rows, cols, p["k"], P])
+            elif k == "reduce":
+                # the reduce forms of MEAN_LAST / MEAN_MID (a mean is one
+                # of five functions): [x, y, scratch|null] and
+                # [rows, cols, fn, P] or [d0, d1, d2, fn, P]
+                outer, red, inner = self._reduce_view(op)
+                P = reduce_segments(outer, red, inner)
+                ptrs = io(op, 1) + [self._scratch(oi) if P > 1 else None]
+                fn = _REDUCE_CODE[p["fn"]]
+                if inner == 1:
+                    call("MEAN_LAST", ptrs, [outer, red, fn, P])
+                else:
+                    call("MEAN_MID", ptrs, [outer, red, inner, fn, P])
             elif k == "layernorm":
                 call("LAYERNORM", io(op, 3), _rows_cols(xs),
                      [float(p["eps"])])

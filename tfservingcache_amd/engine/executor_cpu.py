@@ -198,9 +198,19 @@ class CpuExecutor:
             x = _get(op.inputs[0])
             y = x.mean(axis=-1, keepdims=p.get("keep", False))
             vals[op.outputs[0]] = y.astype(np.float32)
+        elif k == "reduce":
+            # the middle axis of the [outer, red, inner] view
+            x = _get(op.inputs[0])
+            f = {"mean": np.mean, "sum": np.sum, "max": np.max,
+                 "min": np.min, "prod": np.prod}[p["fn"]]
+            y = f(x.reshape(self.plan.resolve_shape(p["view"], batch)),
+                  axis=1)
+            out_shape = self.plan.resolve_shape(
+                self.plan.tensors[op.outputs[0]].shape, batch)
+            vals[op.outputs[0]] = y.astype(np.float32).reshape(out_shape)
         elif k == "softmax":
             x = _get(op.inputs[0])
-            mx = x.max(axis=-1, keepdims=True)
+            mx =x.max(axis=-1, keepdims=True)
             e = np.exp(x - mx)
             vals[op.outputs[0]] = (e / e.sum(axis=-1, keepdims=True)).astype(
                 np.float32)

@@ -423,6 +423,9 @@ class _Lowerer:
         if op == "Mean":
             self.lower_mean(nd, out)
             return
+        if op in ("Sum", "Max", "Min", "Prod"):
+            self.lower_reduce(nd, out)
+            return
         if op == "Softmax":
             x = self.tid(nd.input[0])
             shape = self.tensors[x].shape
@@ -1544,7 +1547,78 @@ class _Lowerer:
             self.ops.append(PlanOp("reduce_mean_mid", [x], [y],
                                    {"keep": keep}))
             return
-        raise PlanError(f"Mean over axes {axes} unsupported")
+        self.lower_reduce(nd, out)
+
+    _REDUCE_FN = {"Mean": "mean", "Sum": "sum", "Max": "max", "Min": "min",
+                  "Prod": "prod"}
+
+    def lower_reduce(self, nd: g.NodeDef, out: str) -> None:
+        """Sum / Max / Min / Prod, and every Mean lower_mean has no
+        pattern for -> `reduce` ops. Size-1 dims are dropped and adjacent
+        kept / reduced dims merged, so one op sees a view
+        [outer, red, inner] (outer and inner may be 1; outer is symbolic
+        when it holds the batch) and reduces its middle axis. Separated
+        reduced runs (axes [1, 3] of rank 4) become successive ops,
+        innermost run first; all five functions compose that way."""
+        fn = self._REDUCE_FN[nd.op]
+        who = f"{nd.op} {nd.name}"
+        x = self.tid(nd.input[0])
+        xt = self.tensors[x]
+        xs = tuple(xt.shape)
+        if xt.dtype != "f32":
+            raise PlanError(f"{who}: only f32 input supported")
+        axes_v = self.const_value(nd.input[1]) if len(nd.input) > 1 else None
+        if axes_v is None:
+            raise PlanError(f"{who}: dynamic axes unsupported")
+        axes = [int(a) for a in np.atleast_1d(axes_v)]
+        rank = len(xs)
+        if any(a < -rank or a >= rank for a in axes):
+            raise PlanError(f"{who}: axes {axes} outside the input's rank "
+                            f"{rank} (unknown or wrong shape {xs})")
+        axes = sorted({a % rank for a in axes})
+        keep = _attr_b(nd, "keep_dims", False)
+        if any(is_sym(xs[a]) for a in axes):
+            raise PlanError(f"{who}: cannot reduce the batch axis "
+                            f"(axes {axes} of {xs})")
+        out_shape = tuple(1 if d in axes else s for d, s in enumerate(xs)
+                          if keep or d not in axes)
+        # runs of reduced dims over the dims of size != 1
+        dims = [(s, d in axes) for d, s in enumerate(xs) if s != 1]
+        runs: List[List] = []                 # [size, reduced]
+        for s, r in dims:
+            if runs and runs[-1][1] == r:
+                runs[-1][0] *= s        # -k (k*B) times n is -(k*n)
+            else:
+                runs.append([s, r])
+        n_red = sum(1 for _s, r in runs if r)
+        if n_red == 0:
+            # nothing to fold (no axes, or only size-1 ones): a view
+            self.new_tensor(out_shape, "f32", xt.kind, out,
+                            weight=(xt.weight.reshape(out_shape)
+                                    if xt.weight is not None else None),
+                            alias_of=(x if xt.kind != "weight" else None))
+            return
+        cur = x
+        for step in range(n_red):
+            i = max(j for j, (_s, r) in enumerate(runs) if r)
+            outer = inner = 1
+            for s, _r in runs[:i]:
+                outer *= s
+            for s, _r in runs[i + 1:]:
+                inner *= s
+            red = runs[i][0]
+            last = step == n_red - 1
+            shape = out_shape if last else \
+                tuple(s for j, (s, _r) in enumerate(runs) if j != i)
+            y = self.new_tensor(shape, "f32", "activation",
+                                out if last else "")
+            self.ops.append(PlanOp("reduce", [cur], [y], {
+                "fn": fn, "view": (outer, red, inner), "keep": keep}))
+            cur = y
+            # the run is gone; its kept neighbours are now adjacent
+            runs = runs[:i] + runs[i + 1:]
+            if 0 < i < len(runs):
+                runs[i - 1:i + 1] = [[runs[i - 1][0] * runs[i][0], False]]
 
     def lower_pad(self, nd: g.NodeDef, out: str) -> None:
         x = self.tid(nd.input[0])

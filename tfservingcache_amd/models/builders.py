@@ -495,6 +495,90 @@ def build_retrieval(d_query=32, d_hidden=64, d_embed=32, n_items=3001,
 
 
 # ---------------------------------------------------------------------------
+# Pooling text encoder in front of a retrieval head: token embeddings,
+# masked mean and masked max pooling over the tokens, a dense tanh layer,
+# tf.math.l2_normalize, cosine scores against a constant candidate matrix
+# and tf.math.top_k. The reductions are the point: two Sums (pooling), a
+# Max, and the Sum(-1, keep_dims) inside l2_normalize.
+# ---------------------------------------------------------------------------
+def build_pooling_encoder(vocab=101, seq_len=12, d_embed=32, d_out=32,
+                          n_items=257, k=5, seed=0):
+    """Inputs `input_ids`, `input_mask` (int32 [B, seq_len], 1 = token).
+    Signature outputs: `scores` [B, k], `ids` [B, k] (i32), `embedding`
+    [B, d_out] (unit length) and `logits` [B, n_items]."""
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+    i32 = gb.a_type(3)
+
+    def c(name, v, dtype=np.float32):
+        return gb.const(name, np.asarray(v, dtype=dtype))
+
+    def W(name, shape, scale):
+        return c(name, rng.standard_normal(shape) * scale)
+
+    ids = gb.placeholder("input_ids", np.int32, [-1, seq_len],
+                         signature_name="input_ids")
+    mask = gb.placeholder("input_mask", np.int32, [-1, seq_len],
+                          signature_name="input_mask")
+    ids_flat = gb.node("Reshape", "ids_flat", [ids, c("flat", [-1], np.int32)])
+    emb = gb.node("GatherV2", "embed",
+                  [W("embeddings", (vocab, d_embed), 1.0), ids_flat,
+                   c("gather_axis", 0, np.int32)], Tparams=f32, Tindices=i32)
+    emb = gb.node("Reshape", "embed3",
+                  [emb, c("to_bsd", [-1, seq_len, d_embed], np.int32)])
+    mask_f = gb.node("Cast", "mask/cast", [mask], SrcT=i32, DstT=f32)
+    mask3 = gb.node("ExpandDims", "mask/expand",
+                    [mask_f, c("mask/axis", -1, np.int32)], T=f32)
+    tokens = c("pool/axis", [1], np.int32)
+
+    # masked mean: Sum(x * mask, 1) / Maximum(Sum(mask, 1), eps)
+    xm = gb.node("Mul", "pool/masked", [emb, mask3], T=f32)
+    tok_sum = gb.node("Sum", "pool/sum", [xm, tokens], T=f32,
+                      keep_dims=gb.a_bool(False))
+    count = gb.node("Sum", "pool/count", [mask_f, tokens], T=f32,
+                    keep_dims=gb.a_bool(True))
+    count = gb.node("Maximum", "pool/count_eps",
+                    [count, c("pool/eps", 1e-9)], T=f32)
+    mean = gb.node("RealDiv", "pool/mean", [tok_sum, count], T=f32)
+
+    # masked max: padding tokens are pushed to -1e4 before the Max
+    off = gb.node("Sub", "pool/off", [mask3, c("pool/one", 1.0)], T=f32)
+    off = gb.node("Mul", "pool/neg", [off, c("pool/big", 1.0e4)], T=f32)
+    xo = gb.node("AddV2", "pool/offset", [xm, off], T=f32)
+    mx = gb.node("Max", "pool/max", [xo, tokens], T=f32,
+                 keep_dims=gb.a_bool(False))
+
+    cat = gb.node("ConcatV2", "pool/concat",
+                  [mean, mx, c("pool/cat_axis", 1, np.int32)], T=f32,
+                  N=gb.a_int(2))
+    h = gb.node("MatMul", "proj/mm",
+                [cat, W("proj/w", (2 * d_embed, d_out),
+                        np.sqrt(0.5 / d_embed))], T=f32)
+    h = gb.node("BiasAdd", "proj/bias",
+                [h, W("proj/b", (d_out,), 0.1)], T=f32)
+    h = gb.node("Tanh", "proj/tanh", [h], T=f32)
+
+    # tf.math.l2_normalize(h, axis=-1)
+    sq = gb.node("Square", "l2/square", [h], T=f32)
+    ss = gb.node("Sum", "l2/sum", [sq, c("l2/axis", [-1], np.int32)], T=f32,
+                 keep_dims=gb.a_bool(True))
+    ss = gb.node("Maximum", "l2/max", [ss, c("l2/eps", 1e-12)], T=f32)
+    inv = gb.node("Rsqrt", "l2/rsqrt", [ss], T=f32)
+    e = gb.node("Mul", "embedding", [h, inv], T=f32)
+
+    logits = gb.node("MatMul", "logits",
+                     [e, W("candidates", (d_out, n_items), 1.0)], T=f32)
+    top = gb.node("TopKV2", "top_k", [logits, c("k", k, np.int32)],
+                  T=f32, sorted=gb.a_bool(True), index_type=i32)
+    gb.mark_output("scores", f"{top}:0")
+    gb.mark_output("ids", f"{top}:1")
+    gb.mark_output("embedding", e)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # U-Net (inference): two-level encoder-decoder with skip connections —
 # the upsampling model family (segmentation heads, FPN necks,
 # autoencoder decoders). conv+BN+ReLU throughout; the decoder upsamples
