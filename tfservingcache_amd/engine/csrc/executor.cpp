@@ -152,15 +152,18 @@ static void launch_call(const Call& c, hipStream_t s) {
       break;
     case K_CONV: {
       // ptrs: [x, w, bias, residual|0, zeros, y]
-      // ints: [N,H,W,C,Kc,R,S,sh,sw,pt,pl,Ho,Wo,k_pad,act(,groups)];
-      // the 15-int form is a dense conv
+      // ints: [N,H,W,C,Kc,R,S,sh,sw,pt,pl,Ho,Wo,k_pad,act(,groups
+      // (,dh,dw))]; the 15-int form is a dense conv, the 18-int form a
+      // dilated one (groups written as 1)
       const ushort* res = c.ptrs[3] ? cp(3) : nullptr;
       launch_conv_igemm(s, cp(0), cp(1), cp(2), res, cp(4), p(5),
                         int(I[0]), int(I[1]), int(I[2]), int(I[3]),
                         int(I[4]), int(I[5]), int(I[6]), int(I[7]),
                         int(I[8]), int(I[9]), int(I[10]), int(I[11]),
                         int(I[12]), int(I[13]), int(I[14]),
-                        I.size() > 15 ? int(I[15]) : 1);
+                        I.size() > 15 ? int(I[15]) : 1,
+                        I.size() > 17 ? int(I[16]) : 1,
+                        I.size() > 17 ? int(I[17]) : 1);
       break;
     }
     case K_PAD_LAST:
@@ -229,12 +232,15 @@ static void launch_call(const Call& c, hipStream_t s) {
       // ptrs: [x, w, bias, y]
       // ints: [N,H,W,C,R,S,sh,sw,pt,pl,Ho,Wo,act] and an optional
       // 14th, the depth multiplier M (absent = 1); C is the INPUT
-      // channel count, w / bias / y have C*M channels
+      // channel count, w / bias / y have C*M channels. The 16-int form
+      // [..., act, M, dh, dw] is a dilated depthwise conv (M == 1)
       launch_depthwise_conv(s, cp(0), cp(1), cp(2), p(3), int(I[0]),
                             int(I[1]), int(I[2]), int(I[3]), int(I[4]),
                             int(I[5]), int(I[6]), int(I[7]), int(I[8]),
                             int(I[9]), int(I[10]), int(I[11]),
-                            int(I[12]), I.size() > 13 ? int(I[13]) : 1);
+                            int(I[12]), I.size() > 13 ? int(I[13]) : 1,
+                            I.size() > 15 ? int(I[14]) : 1,
+                            I.size() > 15 ? int(I[15]) : 1);
       break;
     case K_RESIZE: {
       // ptrs: [x, y]
@@ -481,6 +487,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
 
   mod.def("topk_sort_max_cols", &tfsc::topk_sort_max_cols);
   mod.def("set_topk_sort_max_cols", &tfsc::set_topk_sort_max_cols);
+  mod.def("conv_dilated_skip", &tfsc::conv_dilated_skip);
+  mod.def("set_conv_dilated_skip", &tfsc::set_conv_dilated_skip);
   mod.def("reduce_wave_max_cols", &tfsc::reduce_wave_max_cols);
   mod.def("reduce_cols_tx_max", &tfsc::reduce_cols_tx_max);
   mod.def("reduce_cols_wg_target", &tfsc::reduce_cols_wg_target);

@@ -145,12 +145,26 @@ void launch_batched_gemm(hipStream_t s, const ushort* A, const ushort* B,
 // channels g*Ng.. (Ng = Kc/groups, Ng % 8 == 0); w is
 // [Kc][pad64(R*S*Cg)], row g*Ng + n being group g's filter n, and
 // k_pad = pad64(R*S*Cg).
+// (dh, dw) != (1, 1) is a dilated (atrous) conv on its own kernel: tap
+// (r, s) reads hi = ho*sh - pt + r*dh, wi = wo*sw - pl + s*dw; w and
+// k_pad = pad64(R*S*C) are laid out as for dilation 1. When C % 64 == 0
+// the kernel can skip the K tiles of taps that lie outside the image for
+// a whole M tile (see set_conv_dilated_skip). Throws before any launch on dh < 1 or dw < 1, on a
+// dilation with groups > 1, and on a dilation with C % 8 != 0.
+// dh == dw == 1 runs exactly the kernels described above.
 void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        const ushort* bias, const ushort* residual,
                        const ushort* zeros, ushort* y,
                        int N, int H, int W, int C, int Kc, int R, int S,
                        int sh, int sw, int pt, int pl, int Ho, int Wo,
-                       int k_pad, int act, int groups = 1);
+                       int k_pad, int act, int groups = 1, int dh = 1,
+                       int dw = 1);
+// dead-tap skipping of the dilated kernel: 0 never, 1 where it pays
+// (default: more than one block per CU and a filter reach of at least an
+// eighth of the image), 2 wherever C % 64 == 0. A measurement switch
+// (scripts/dilated_conv_probe.py)
+int conv_dilated_skip();
+void set_conv_dilated_skip(int mode);
 
 // im2col for NHWC conv: out[N*Ho*Wo, K_pad] where the first R*S*C columns
 // hold the patch elements (r,s,c order, c fastest) and columns >= R*S*C
@@ -178,11 +192,16 @@ void launch_im2col(hipStream_t s, const ushort* x, ushort* y,
 // M in {2,4} or M % 8 == 0, one output element per thread otherwise.
 // mult == 1 runs exactly the kernels described above. Throws on
 // mult < 1 before any launch.
+// (dh, dw) != (1, 1) with mult == 1 is the atrous separable case
+// (K_DEPTHWISE's optional 15th and 16th ints): tap (r, s) reads
+// hi = ho*sh - pt + r*dh, wi = wo*sw - pl + s*dw, 8 channels per thread
+// when C % 8 == 0, one output element per thread otherwise. Throws before
+// any launch on dh < 1 or dw < 1 and on a dilation with mult > 1.
 void launch_depthwise_conv(hipStream_t s, const ushort* x, const ushort* w,
                            const ushort* bias, ushort* y,
                            int N, int H, int W, int C, int R, int S,
                            int sh, int sw, int pt, int pl, int Ho, int Wo,
-                           int act, int mult = 1);
+                           int act, int mult = 1, int dh = 1, int dw = 1);
 
 // NHWC image resize with TF's coordinate rules (ResizeNearestNeighbor /
 // ResizeBilinear): mode 0 = nearest, 1 = bilinear. The per-axis scale is

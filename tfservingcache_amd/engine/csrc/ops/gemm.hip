@@ -693,6 +693,276 @@ void conv_igemm_grouped_kernel(const ushort* __restrict__ x,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Dilated (atrous) implicit-GEMM conv (DeepLab / dilated-ResNet / ASPP):
+//   hi = ho*sh - pt + r*dh,  wi = wo*sw - pl + s*dw
+// Same anatomy as conv_igemm_kernel (128x128x64 tiles, 16-byte glds
+// staging with the XOR source swizzle, two LDS buffers, one barrier per K
+// tile, 16x16x32 bf16 MFMA, epilogue_store, XCD swizzle), with the
+// m -> (n, ho, wo) decomposition of a lane's four A rows hoisted out of
+// the K loop as in the grouped kernel.
+//
+// Dead-tap skipping (SKIP): at ASPP rates on small maps a whole row or
+// column of filter taps lies outside the image for every row of an M
+// tile; a dense K loop would stage zeros and run MFMAs on them. With
+// C % 64 == 0 a K tile lies inside one tap (r, s), and K = R*S*C has no
+// pad tile. The prologue reduces min/max of hi0 and wi0 over the block's
+// 128 rows (wave shuffles, then the four waves through LDS: one extra
+// barrier), builds a bit mask of the taps that can touch the image for
+// some row of the block - conservative: it may keep a dead tap and never
+// drops a live one - and the K loop visits live K tiles only; "next tile"
+// of the double-buffer pipeline is the next live one. All of it is
+// block-uniform scalar code. No live tile at all (huge explicit pads) is
+// legal: the accumulators stay zero and the epilogue writes
+// act(bias [+ residual]) everywhere. The launcher picks SKIP only when
+// C % 64 == 0 and R*S <= 64 (the mask's width).
+// ---------------------------------------------------------------------------
+// The new float arithmetic below is compiled without packed f32
+// instructions (v_pk_add_f32 and kin), as in ops/reduce.hip: the
+// extension's flags are shared by every source, so the feature is
+// switched off here, for the device pass only, and back on after.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                   \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+struct DilatedConvGeom {
+  int H, W, C, R, S, sh, sw, pt, pl, dh, dw, Ho, Wo, rsc;
+};
+
+TFSC_DEV int wave_min(int v) {
+  #pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    int t = __shfl_xor(v, o, WAVE);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
+TFSC_DEV int wave_max(int v) {
+  #pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    int t = __shfl_xor(v, o, WAVE);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+template <bool HAS_RES, bool SKIP>
+__global__ __launch_bounds__(THREADS)
+void conv_igemm_dilated_kernel(const ushort* __restrict__ x,
+                               const ushort* __restrict__ B,
+                               const ushort* __restrict__ bias,
+                               const ushort* __restrict__ residual,
+                               const ushort* __restrict__ zeros,
+                               ushort* __restrict__ Cout,
+                               int M, int N, int K, int act,
+                               DilatedConvGeom g, int n_tiles_m) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * BM * BK * 2];
+  auto lds_a = [&](int buf) -> char* { return smem + buf * 32768; };
+  auto lds_b = [&](int buf) -> char* { return smem + 16384 + buf * 32768; };
+
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int tile_m = bid % n_tiles_m;
+  const int tile_n = bid / n_tiles_m;
+  const int m0 = tile_m * BM;
+  const int n0 = tile_n * BN;
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r_in = lane >> 3;
+  const int chunk_src = (lane & 7) ^ r_in;    // row & 7 == r_in
+
+  // the lane's four A rows never change: decompose m -> (n, ho, wo) once
+  int hi0[4], wi0[4], nH[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int m = m0 + wave * 32 + i * 8 + r_in;
+    m = m < M - 1 ? m : M - 1;
+    int wo = m % g.Wo;
+    int t = m / g.Wo;
+    hi0[i] = (t % g.Ho) * g.sh - g.pt;
+    wi0[i] = wo * g.sw - g.pl;
+    nH[i] = (t / g.Ho) * g.H;
+  }
+
+  // live-tap mask: bit r*S + s is clear when tap (r, s) is out of the
+  // image for every one of the block's rows
+  unsigned long long live = ~0ull;
+  const int tiles_per_tap = g.C / BK;         // SKIP: C % 64 == 0
+  if (SKIP) {
+    int lo_h = hi0[0], hi_h = hi0[0], lo_w = wi0[0], hi_w = wi0[0];
+    #pragma unroll
+    for (int i = 1; i < 4; ++i) {
+      lo_h = hi0[i] < lo_h ? hi0[i] : lo_h;
+      hi_h = hi0[i] > hi_h ? hi0[i] : hi_h;
+      lo_w = wi0[i] < lo_w ? wi0[i] : lo_w;
+      hi_w = wi0[i] > hi_w ? wi0[i] : hi_w;
+    }
+    lo_h = wave_min(lo_h); hi_h = wave_max(hi_h);
+    lo_w = wave_min(lo_w); hi_w = wave_max(hi_w);
+    // buffer 1 is first written after the K loop's first barrier, so its
+    // head is free to carry the four waves' partials until then
+    int* red = reinterpret_cast<int*>(lds_a(1));
+    if (lane == 0) {
+      red[wave * 4 + 0] = lo_h; red[wave * 4 + 1] = hi_h;
+      red[wave * 4 + 2] = lo_w; red[wave * 4 + 3] = hi_w;
+    }
+    __syncthreads();
+    #pragma unroll
+    for (int w_ = 0; w_ < N_WAVES; ++w_) {
+      int a = red[w_ * 4 + 0], b = red[w_ * 4 + 1];
+      int c = red[w_ * 4 + 2], d = red[w_ * 4 + 3];
+      lo_h = a < lo_h ? a : lo_h; hi_h = b > hi_h ? b : hi_h;
+      lo_w = c < lo_w ? c : lo_w; hi_w = d > hi_w ? d : hi_w;
+    }
+    lo_h = __builtin_amdgcn_readfirstlane(lo_h);
+    hi_h = __builtin_amdgcn_readfirstlane(hi_h);
+    lo_w = __builtin_amdgcn_readfirstlane(lo_w);
+    hi_w = __builtin_amdgcn_readfirstlane(hi_w);
+    live = 0;
+    for (int r = 0; r < g.R; ++r) {
+      bool row_dead = (hi_h + r * g.dh < 0) | (lo_h + r * g.dh >= g.H);
+      for (int s = 0; s < g.S; ++s) {
+        bool dead = row_dead | (hi_w + s * g.dw < 0) |
+                    (lo_w + s * g.dw >= g.W);
+        if (!dead) live |= 1ull << (r * g.S + s);
+      }
+    }
+  }
+
+  // The K loop runs over live tiles only. SKIP: `rest` holds the live taps
+  // not yet staged, its lowest set bit the tap being staged, `j` the tile
+  // inside that tap; the tap's (r*dh, s*dw) are scalars recomputed only
+  // when the tap changes, so the per-tile k -> (r, s, c) divisions of the
+  // dense kernel go away too. !SKIP: tile i is K tile i.
+  const int n_live = SKIP ? __builtin_popcountll(live) * tiles_per_tap
+                          : K / BK;
+  unsigned long long rest = live;
+  int j = 0, tap = 0, dr = 0, ds = 0;
+  auto enter_tap = [&]() {
+    tap = __builtin_ctzll(rest);
+    dr = (tap / g.S) * g.dh;
+    ds = (tap % g.S) * g.dw;
+  };
+  if (SKIP && n_live) enter_tap();
+
+  // stage live tile `i` (SKIP: the tile the cursor stands on, then step)
+  auto stage = [&](int i, int buf) {
+    int k0, c, r_dh, s_dw;
+    bool k_ok = true;
+    if (SKIP) {
+      k0 = (tap * tiles_per_tap + j) * BK;
+      c = j * BK + chunk_src * 8;
+      r_dh = dr; s_dw = ds;
+      if (++j == tiles_per_tap) {
+        j = 0;
+        rest &= rest - 1;
+        if (rest) enter_tap();
+      }
+    } else {
+      k0 = i * BK;
+      int k = k0 + chunk_src * 8;         // start of the 8-channel chunk
+      c = k % g.C;
+      int t2 = k / g.C;
+      s_dw = (t2 % g.S) * g.dw;
+      r_dh = (t2 / g.S) * g.dh;
+      k_ok = k < g.rsc;
+    }
+    char* lds_tile = lds_a(buf);
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      int hi = hi0[q] + r_dh, wi = wi0[q] + s_dw;
+      bool ok = k_ok & (hi >= 0) & (hi < g.H) & (wi >= 0) & (wi < g.W);
+      const ushort* gptr = ok
+          ? x + ((int64_t)(nH[q] + hi) * g.W + wi) * g.C + c
+          : zeros;
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const uint32_t*>(gptr),
+          reinterpret_cast<uint32_t*>(lds_tile + (wave * 32 + q * 8) * 128),
+          16, 0, 0);
+    }
+    stage_tile_glds<128, 4>(B, K, N - 1, n0, k0, lds_b(buf), wave, lane);
+  };
+
+  f32x4_t acc[4][4] = {};
+
+  if (n_live) stage(0, 0);
+
+  int cur = 0;
+  for (int i = 0; i < n_live; ++i) {
+    __syncthreads();
+    if (i + 1 < n_live) stage(i + 1, cur ^ 1);
+    const char* at = lds_a(cur);
+    const char* bt = lds_b(cur);
+    const int frow = lane & 15;
+    const int kgrp = lane >> 4;
+    #pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8_t a_frag[4], b_frag[4];
+      const int chunk = ks * 4 + kgrp;
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        a_frag[mi] = *reinterpret_cast<const bf16x8_t*>(
+            at + lds_off(wm * 64 + mi * 16 + frow, chunk));
+      #pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+        b_frag[ni] = *reinterpret_cast<const bf16x8_t*>(
+            bt + lds_off(wn * 64 + ni * 16 + frow, chunk));
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_frag[mi], b_frag[ni], acc[mi][ni], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    cur ^= 1;
+  }
+
+  epilogue_store<true, HAS_RES>(acc, smem, bias, residual, Cout, M, N,
+                                m0, n0, wave, lane, wm, wn, act, 1.0f);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+// Dead-tap skipping: 0 never, 1 where it pays (default), 2 wherever the
+// kernel can (C % 64 == 0, R*S <= 64). A measurement switch
+// (scripts/dilated_conv_probe.py). Measured on an MI355X
+// (profiles/dilated_conv.md), the skipping kernel is 12-23% faster than
+// the same kernel without it at [8,65,65,512] rates 12-36 and 2-4% slower
+// where nothing can be gained: when the grid has at most one block per
+// CU, the kernel lasts as long as its slowest block, which sits in the
+// middle of the image and skips nothing; and when the dilated filter
+// reaches over less than an eighth of the image, hardly a block lies
+// wholly in the border where taps die. Mode 1 skips outside those cases.
+static int g_dilated_skip = 1;
+int conv_dilated_skip() { return g_dilated_skip; }
+void set_conv_dilated_skip(int mode) { g_dilated_skip = mode; }
+
+static void conv_dilated_launch(hipStream_t s, const ushort* x,
+                                const ushort* w, const ushort* bias,
+                                const ushort* residual, const ushort* zeros,
+                                ushort* y, int M, int Kc, int k_pad, int act,
+                                const DilatedConvGeom& g) {
+  int ntm = int(ceil_div(M, BM)), ntn = int(ceil_div(Kc, BN));
+  dim3 grid(ntm * ntn);
+  bool skip = g_dilated_skip && g.C % BK == 0 && g.R * g.S <= 64;
+  if (skip && g_dilated_skip == 1)
+    skip = grid.x > 256 && ((g.R - 1) * g.dh * 8 >= g.H ||
+                            (g.S - 1) * g.dw * 8 >= g.W);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, x, w, bias, residual,
+                       zeros, y, M, Kc, k_pad, act, g, ntm);
+  };
+  if (residual && skip) launch(conv_igemm_dilated_kernel<true, true>);
+  else if (residual)    launch(conv_igemm_dilated_kernel<true, false>);
+  else if (skip)        launch(conv_igemm_dilated_kernel<false, true>);
+  else                  launch(conv_igemm_dilated_kernel<false, false>);
+}
+
 template <int NT>
 static void conv_grouped_launch(hipStream_t s, const ushort* x,
                                 const ushort* w, const ushort* bias,
@@ -716,9 +986,29 @@ void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        const ushort* zeros, ushort* y,
                        int N_img, int H, int W, int C, int Kc, int R,
                        int S, int sh, int sw, int pt, int pl, int Ho,
-                       int Wo, int k_pad, int act, int groups) {
+                       int Wo, int k_pad, int act, int groups, int dh,
+                       int dw) {
   if (groups < 1)
     throw std::runtime_error("conv_igemm groups must be >= 1");
+  if (dh < 1 || dw < 1)
+    throw std::runtime_error("conv_igemm dilation must be >= 1");
+  if (dh != 1 || dw != 1) {
+    if (groups > 1)
+      throw std::runtime_error("dilated grouped conv_igemm unsupported");
+    if (C % 8 != 0)
+      throw std::runtime_error("dilated conv_igemm requires C % 8 == 0");
+    if (k_pad != (R * S * C + BK - 1) / BK * BK)
+      throw std::runtime_error(
+          "dilated conv_igemm k_pad must be pad64(R*S*C)");
+    if ((int64_t)(R - 1) * dh >= (1 << 30) ||
+        (int64_t)(S - 1) * dw >= (1 << 30))
+      throw std::runtime_error("dilated conv_igemm: filter extent too large");
+    DilatedConvGeom g{H, W, C, R, S, sh, sw, pt, pl, dh, dw, Ho, Wo,
+                      R * S * C};
+    conv_dilated_launch(s, x, w, bias, residual, zeros, y, N_img * Ho * Wo,
+                        Kc, k_pad, act, g);
+    return;
+  }
   if (groups > 1) {
     if (C % groups != 0 || Kc % groups != 0)
       throw std::runtime_error(

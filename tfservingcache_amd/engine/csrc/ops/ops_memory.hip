@@ -863,14 +863,136 @@ __global__ void k_depthwise_mult_scalar(const ushort* __restrict__ x,
   }
 }
 
+// Dilated (atrous) depthwise, depth_multiplier == 1: the DeepLab /
+// Xception / MobileNet atrous separable conv. Tap (r, s) reads
+// (hi0 + r*dh, wi0 + s*dw); a tap outside the image is skipped without
+// being read, so at a rate beyond the image only the centre tap costs
+// anything. Same design as k_depthwise_mult_v8: one thread owns 8
+// channels of one output pixel, one 16-byte x load and one 16-byte w load
+// per tap, f32 accumulation from the bias, one rounding, one 16-byte
+// store. The taps of one pixel are dh*W*C elements apart, so unlike
+// dilation 1 neighbouring taps share no cache line; neighbouring threads
+// (channels, then wo) still do.
+// The new float arithmetic below is compiled without packed f32
+// instructions (v_pk_add_f32 and kin), as in ops/reduce.hip: the
+// extension's flags are shared by every source, so the feature is
+// switched off here, for the device pass only, and back on after.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                   \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+__global__ void k_depthwise_dilated_v8(const ushort* __restrict__ x,
+                                       const ushort* __restrict__ w,
+                                       const ushort* __restrict__ bias,
+                                       ushort* __restrict__ y,
+                                       int N, int H, int W, int C, int R,
+                                       int S, int sh, int sw, int pt, int pl,
+                                       int dh, int dw, int Ho, int Wo,
+                                       int act) {
+  int c8 = C / 8;
+  int64_t total = (int64_t)N * Ho * Wo * c8;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < total; i += stride) {
+    int64_t t = i;
+    int cv = int(t % c8); t /= c8;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    float acc[8];
+    short8_t bv = reinterpret_cast<const short8_t*>(bias)[cv];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bf2f((ushort)bv[j]);
+    int hi0 = ho * sh - pt, wi0 = wo * sw - pl;
+    for (int r = 0; r < R; ++r) {
+      int hi = hi0 + r * dh;
+      if (hi < 0 || hi >= H) continue;
+      for (int sx = 0; sx < S; ++sx) {
+        int wi = wi0 + sx * dw;
+        if (wi < 0 || wi >= W) continue;
+        short8_t xv = reinterpret_cast<const short8_t*>(
+            x + ((((int64_t)n * H + hi) * W + wi) * C))[cv];
+        short8_t wv = reinterpret_cast<const short8_t*>(
+            w + ((int64_t)(r * S + sx) * C))[cv];
+        #pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc[j] += bf2f((ushort)xv[j]) * bf2f((ushort)wv[j]);
+      }
+    }
+    short8_t out;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j)
+      out[j] = (short)f2bf(dw_act(acc[j], act));
+    reinterpret_cast<short8_t*>(
+        y + ((((int64_t)n * Ho + ho) * Wo + wo) * C))[cv] = out;
+  }
+}
+
+// every other C: one thread per output element
+__global__ void k_depthwise_dilated_scalar(const ushort* __restrict__ x,
+                                           const ushort* __restrict__ w,
+                                           const ushort* __restrict__ bias,
+                                           ushort* __restrict__ y,
+                                           int N, int H, int W, int C, int R,
+                                           int S, int sh, int sw, int pt,
+                                           int pl, int dh, int dw, int Ho,
+                                           int Wo, int act) {
+  int64_t total = (int64_t)N * Ho * Wo * C;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < total; i += stride) {
+    int64_t t = i;
+    int c = int(t % C); t /= C;
+    int wo = int(t % Wo); t /= Wo;
+    int ho = int(t % Ho); int n = int(t / Ho);
+    float acc = bf2f(bias[c]);
+    int hi0 = ho * sh - pt, wi0 = wo * sw - pl;
+    for (int r = 0; r < R; ++r) {
+      int hi = hi0 + r * dh;
+      if (hi < 0 || hi >= H) continue;
+      for (int sx = 0; sx < S; ++sx) {
+        int wi = wi0 + sx * dw;
+        if (wi < 0 || wi >= W) continue;
+        acc += bf2f(x[(((int64_t)n * H + hi) * W + wi) * C + c]) *
+               bf2f(w[(int64_t)(r * S + sx) * C + c]);
+      }
+    }
+    y[i] = f2bf(dw_act(acc, act));
+  }
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 void launch_depthwise_conv(hipStream_t s, const ushort* x, const ushort* w,
                            const ushort* bias, ushort* y,
                            int N, int H, int W, int C, int R, int S,
                            int sh, int sw, int pt, int pl, int Ho, int Wo,
-                           int act, int mult) {
+                           int act, int mult, int dh, int dw) {
   if (mult < 1)
     throw std::runtime_error("depthwise conv: depth multiplier " +
                              std::to_string(mult) + " < 1");
+  if (dh < 1 || dw < 1)
+    throw std::runtime_error("depthwise conv: dilation must be >= 1");
+  if (dh != 1 || dw != 1) {
+    if (mult > 1)
+      throw std::runtime_error(
+          "dilated depthwise conv with a depth multiplier unsupported");
+    if ((int64_t)(R - 1) * dh >= (1 << 30) ||
+        (int64_t)(S - 1) * dw >= (1 << 30))
+      throw std::runtime_error("depthwise conv: filter extent too large");
+    if (C % 8 == 0)
+      hipLaunchKernelGGL(k_depthwise_dilated_v8,
+                         dim3(grid_for((int64_t)N * Ho * Wo * (C / 8))),
+                         dim3(TPB), 0, s, x, w, bias, y, N, H, W, C, R, S,
+                         sh, sw, pt, pl, dh, dw, Ho, Wo, act);
+    else
+      hipLaunchKernelGGL(k_depthwise_dilated_scalar,
+                         dim3(grid_for((int64_t)N * Ho * Wo * C)),
+                         dim3(TPB), 0, s, x, w, bias, y, N, H, W, C, R, S,
+                         sh, sw, pt, pl, dh, dw, Ho, Wo, act);
+    return;
+  }
   if (mult > 1) {
     int64_t K = (int64_t)C * mult;
     bool vec = K % 8 == 0 && (mult == 2 || mult == 4 || mult % 8 == 0);

@@ -423,6 +423,10 @@ class _Emitter:
                     # optional 14th int, like CONV's 16th `groups`:
                     # c stays the INPUT channel count
                     ints.append(p["mult"])
+                if "dilation" in p:
+                    # 16-int form [..., act, M, dh, dw]; the planner
+                    # admits a dilation with M == 1 only
+                    ints += [1, *p["dilation"]]
                 call("DEPTHWISE", io(op, 3), ints)
             elif k in _ROWWISE:
                 call(_ROWWISE[k], io(op, 1), _rows_cols(xs))
@@ -669,7 +673,17 @@ class _Emitter:
         out = self._ptr(op.outputs[0])
         zeros = (("zeros",), 0)
         groups = p.get("groups", 1)
-        if groups > 1:
+        if "dilation" in p:
+            # dilated implicit-GEMM: the 18-int form [..., act, groups,
+            # dh, dw] with groups written as 1 (the planner rejects a
+            # dilated grouped conv and C % 8 != 0). Never the 1x1 GEMM
+            # shortcut or the channel widening.
+            self._call("CONV",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res,
+                        zeros, out],
+                       [n, H, W, C, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                        _pad64(wR * wS * wC), act, 1, *p["dilation"]])
+        elif groups > 1:
             # grouped implicit-GEMM: the master is [R,S,Cg,K] (Cg % 8 ==
             # 0 by the planner's merge rule), C the input's full channel
             # count; groups rides as an optional 16th int. Never the

@@ -318,12 +318,14 @@ class CpuExecutor:
         Ho, Wo = p["out_hw"]
         xp = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
         G = p.get("groups", 1)
+        dh, dw = p.get("dilation", (1, 1))    # dense convs only
         if G == 1:
-            # im2col
+            # im2col; tap (r, s) starts at (r*dh, s*dw)
             cols = np.empty((N, Ho, Wo, R * S * C), dtype=np.float32)
             for r in range(R):
                 for s in range(S):
-                    patch = xp[:, r:r + sh * Ho:sh, s:s + sw * Wo:sw, :]
+                    patch = xp[:, r * dh:r * dh + sh * Ho:sh,
+                               s * dw:s * dw + sw * Wo:sw, :]
                     cols[..., (r * S + s) * C:(r * S + s + 1) * C] = patch
             y = cols.reshape(-1, R * S * C) @ w.reshape(-1, K)
         else:
@@ -357,13 +359,15 @@ class CpuExecutor:
         pt, pb, pl, pr = p["pads"]
         R, S, K = w.shape
         M = p.get("mult", 1)
+        dh, dw = p.get("dilation", (1, 1))    # M == 1 only
         N = x.shape[0]
         Ho, Wo = p["out_hw"]
         xp = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
         y = np.zeros((N, Ho, Wo, K), dtype=np.float32)
         for r in range(R):
             for s_ in range(S):
-                patch = xp[:, r:r + sh * Ho:sh, s_:s_ + sw * Wo:sw, :]
+                patch = xp[:, r * dh:r * dh + sh * Ho:sh,
+                           s_ * dw:s_ * dw + sw * Wo:sw, :]
                 if M > 1:
                     # each input channel feeds M consecutive outputs
                     patch = np.repeat(patch, M, axis=-1)

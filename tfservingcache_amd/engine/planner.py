@@ -210,6 +210,9 @@ class _Lowerer:
         self.fused: set = set()      # node names absorbed into a fused op
         # final-node-name -> emit callback for pre-pass-matched patterns
         self.pattern_emit: Dict[str, tuple] = {}
+        # conv node name -> (x_ref, (bh, bw), pads, BatchToSpaceND node)
+        # of a folded SpaceToBatchND / conv / BatchToSpaceND sandwich
+        self.atrous: Dict[str, tuple] = {}
 
     # -- tensor bookkeeping ----------------------------------------------
     def new_tensor(self, shape: Shape, dtype: str, kind: str, name: str = "",
@@ -280,6 +283,10 @@ class _Lowerer:
         for nd in self.order:
             if nd.op == "Rsqrt" and nd.name not in self.fused:
                 self.match_layernorm(nd)
+
+        for nd in self.order:
+            if nd.op == "SpaceToBatchND":
+                self.match_atrous_sandwich(nd)
 
         for nd in self.order:
             if nd.name in self.pattern_emit:
@@ -618,9 +625,122 @@ class _Lowerer:
                 break
         return bias, bn, residual, act, cur
 
+    def match_atrous_sandwich(self, s2b: g.NodeDef) -> None:
+        """SpaceToBatchND(x, block=[bh,bw], paddings=P) -> Conv2D |
+        DepthwiseConv2dNative (VALID, stride 1, dilation 1) ->
+        BatchToSpaceND(block=[bh,bw], crops=Cr) is how TF1/slim exports,
+        tf.nn.atrous_conv2d and every dilated tf.nn.depthwise_conv2d
+        spell a dilated conv. It folds into the conv node itself with
+        dilation (bh, bw) and pads
+        (P[0][0], P[0][1] - Cr[0][1], P[1][0], P[1][1] - Cr[1][1]):
+        after padding H' = H + P0 + P1; VALID on each phase, interleaved,
+        gives H' - b(R-1) rows, and cropping c rows at the end equals a
+        dilated conv whose end pad is P1 - c. Folds when block, paddings
+        and crops are constants and each link has a sole consumer;
+        anything else leaves the nodes to be rejected as unsupported ops.
+        A sandwich that matches but cannot be one dilated conv (start
+        crop, negative end pad, mismatched blocks) is a PlanError."""
+        conv = self.sole_consumer(s2b)
+        if conv is None or conv.op not in ("Conv2D", "DepthwiseConv2dNative") \
+                or _node_of(conv.input[0]) != s2b.name:
+            return
+        b2s = self.sole_consumer(conv)
+        if b2s is None or b2s.op != "BatchToSpaceND":
+            return
+        if _attr_s(conv, "padding", "SAME") != "VALID" or \
+                any(v != 1 for v in _attr_ints(conv, "strides") or [1]) or \
+                any(v != 1 for v in _attr_ints(conv, "dilations") or [1]):
+            return
+        consts = [self.const_value(r) for r in
+                  (s2b.input[1], s2b.input[2], b2s.input[1], b2s.input[2])]
+        if any(c is None for c in consts):
+            return
+        block, P, block2, Cr = (np.asarray(c).astype(np.int64)
+                                for c in consts)
+        if block.shape != (2,) or block2.shape != (2,) or \
+                P.shape != (2, 2) or Cr.shape != (2, 2):
+            raise PlanError(
+                f"SpaceToBatchND {s2b.name}: only 2-D blocks fold into a "
+                f"dilated conv (block shape {block.shape})")
+        if not np.array_equal(block, block2):
+            raise PlanError(
+                f"BatchToSpaceND {b2s.name}: block {block2.tolist()} does "
+                f"not match SpaceToBatchND {s2b.name}'s {block.tolist()}")
+        if Cr[0][0] != 0 or Cr[1][0] != 0:
+            raise PlanError(
+                f"BatchToSpaceND {b2s.name}: a start crop "
+                f"({Cr.tolist()}) is not a dilated conv")
+        pads = (int(P[0][0]), int(P[0][1] - Cr[0][1]),
+                int(P[1][0]), int(P[1][1] - Cr[1][1]))
+        if min(pads) < 0 or block.min() < 1:
+            raise PlanError(
+                f"BatchToSpaceND {b2s.name}: crops {Cr.tolist()} exceed "
+                f"SpaceToBatchND {s2b.name}'s paddings {P.tolist()}")
+        self.atrous[conv.name] = (s2b.input[0],
+                                  (int(block[0]), int(block[1])), pads, b2s)
+        self.fused.update((s2b.name, b2s.name))
+
+    def _conv_geometry(self, nd: g.NodeDef, what: str, x_ref: str, R: int,
+                       S: int):
+        """(x tensor, (sh, sw), (dh, dw), pads, (H, W), (Ho, Wo), chain
+        start) of a Conv2D / DepthwiseConv2dNative node, dilation included:
+        the `dilations` attribute [1, dh, dw, 1], or the folded
+        SpaceToBatchND sandwich (match_atrous_sandwich). The dilation of
+        an axis whose filter extent is 1 is normalised to 1; SAME pads
+        and every Ho use the effective extent (R-1)*dh + 1. `chain start`
+        is the node whose consumers _absorb_act_chain follows."""
+        dil = _attr_ints(nd, "dilations") or [1, 1, 1, 1]
+        if len(dil) != 4 or dil[0] != 1 or dil[3] != 1 or min(dil) < 1:
+            raise PlanError(
+                f"dilated {what} {nd.name}: only the H and W axes may be "
+                f"dilated ({dil})")
+        dh, dw = dil[1], dil[2]
+        strides = _attr_ints(nd, "strides") or [1, 1, 1, 1]
+        sh, sw = strides[1], strides[2]
+        padding = _attr_s(nd, "padding", "SAME")
+        start = nd
+        fold = self.atrous.get(nd.name)
+        if fold is not None:
+            x_ref, (dh, dw), pads, start = fold
+            padding = "FOLDED"
+        if R == 1:
+            dh = 1
+        if S == 1:
+            dw = 1
+        x = self.tid(x_ref)
+        xs = self.tensors[x].shape                      # [B,H,W,C]
+        H, W = int(xs[1]), int(xs[2])
+        Re, Se = (R - 1) * dh + 1, (S - 1) * dw + 1
+        if padding == "SAME":
+            Ho, Wo = math.ceil(H / sh), math.ceil(W / sw)
+            pad_h = max((Ho - 1) * sh + Re - H, 0)
+            pad_w = max((Wo - 1) * sw + Se - W, 0)
+            pads = (pad_h // 2, pad_h - pad_h // 2,
+                    pad_w // 2, pad_w - pad_w // 2)
+        elif padding == "VALID":
+            Ho, Wo = (H - Re) // sh + 1, (W - Se) // sw + 1
+            pads = (0, 0, 0, 0)
+        elif padding in ("EXPLICIT", "FOLDED"):
+            if padding == "EXPLICIT":
+                ep = _attr_ints(nd, "explicit_paddings")
+                pads = (ep[2], ep[3], ep[4], ep[5])
+            Ho = (H + pads[0] + pads[1] - Re) // sh + 1
+            Wo = (W + pads[2] + pads[3] - Se) // sw + 1
+        else:
+            raise PlanError(f"{what} padding {padding}")
+        return x, (sh, sw), (dh, dw), pads, (H, W), (Ho, Wo), start
+
     def lower_conv(self, nd: g.NodeDef, out: str) -> None:
-        """Conv2D (NHWC, dilation 1) with BiasAdd / BN / residual /
-        activation folded in -> one conv2d op.
+        """Conv2D (NHWC) with BiasAdd / BN / residual / activation folded
+        in -> one conv2d op.
+
+        Dilation (_conv_geometry: the `dilations` attribute or the
+        SpaceToBatchND sandwich) rides as a `dilation: (dh, dw)` key,
+        present only when it is not (1, 1) - the same rule as `groups` -
+        and sends the op to the dilated implicit-GEMM kernel. That kernel
+        has no grouped form and no channel-widening path, so a dilated
+        grouped conv and a dilated conv on C % 8 != 0 channels are
+        PlanErrors.
 
         A filter [R,S,Cg,K] on an input of C != Cg channels is a grouped
         conv of G = C/Cg groups, Ng = K/G filters each (Keras
@@ -644,19 +764,13 @@ class _Lowerer:
         [56,56,128]) and is kept only because Cg = 1 belongs on a
         depthwise kernel, not on either of these."""
         x_ref, w_ref = nd.input[0], nd.input[1]
-        x = self.tid(x_ref)
         if _attr_s(nd, "data_format", "NHWC") != "NHWC":
             raise PlanError("only NHWC Conv2D supported")
         w = np.asarray(self.weight_of(w_ref), dtype=np.float32)  # [R,S,Cin,K]
-        dil = _attr_ints(nd, "dilations") or [1, 1, 1, 1]
-        if any(d != 1 for d in dil):
-            raise PlanError(f"dilated Conv2D unsupported ({dil})")
-        strides = _attr_ints(nd, "strides") or [1, 1, 1, 1]
-        padding = _attr_s(nd, "padding", "SAME")
-        xs = self.tensors[x].shape                      # [B,H,W,C]
         R, S, Cin, K = w.shape
-        H, W = int(xs[1]), int(xs[2])
-        sh, sw = strides[1], strides[2]
+        x, (sh, sw), (dh, dw), pads, (H, W), (Ho, Wo), start = \
+            self._conv_geometry(nd, "Conv2D", x_ref, R, S)
+        xs = self.tensors[x].shape                      # [B,H,W,C]
         # TF has no `groups` attribute: a grouped Conv2D is a filter whose
         # input-channel dim is C/G
         groups = 1
@@ -673,24 +787,17 @@ class _Lowerer:
                     f"Conv2D {nd.name}: {K} filters do not split into "
                     f"{groups} groups (input {C} channels, filter "
                     f"{w.shape})")
-        if padding == "SAME":
-            Ho, Wo = math.ceil(H / sh), math.ceil(W / sw)
-            pad_h = max((Ho - 1) * sh + R - H, 0)
-            pad_w = max((Wo - 1) * sw + S - W, 0)
-            pads = (pad_h // 2, pad_h - pad_h // 2,
-                    pad_w // 2, pad_w - pad_w // 2)
-        elif padding == "VALID":
-            Ho, Wo = (H - R) // sh + 1, (W - S) // sw + 1
-            pads = (0, 0, 0, 0)
-        elif padding == "EXPLICIT":
-            ep = _attr_ints(nd, "explicit_paddings")
-            pads = (ep[2], ep[3], ep[4], ep[5])
-            Ho = (H + pads[0] + pads[1] - R) // sh + 1
-            Wo = (W + pads[2] + pads[3] - S) // sw + 1
-        else:
-            raise PlanError(f"padding {padding}")
+        if (dh, dw) != (1, 1):
+            if groups > 1:
+                raise PlanError(
+                    f"dilated grouped Conv2D {nd.name} unsupported "
+                    f"({groups} groups, dilation {(dh, dw)})")
+            if is_sym(C) or int(C) % 8 != 0:
+                raise PlanError(
+                    f"dilated Conv2D {nd.name} unsupported on {C} input "
+                    f"channels (needs a multiple of 8)")
 
-        bias, bn, residual, act, final = self._absorb_act_chain(nd)
+        bias, bn, residual, act, final = self._absorb_act_chain(start)
         if bn is not None:
             scale, offset, mean, var, eps = bn
             g_ = scale / np.sqrt(var + eps)
@@ -718,9 +825,13 @@ class _Lowerer:
             params["residual"] = True
         if groups > 1:
             params["groups"] = groups
+        if (dh, dw) != (1, 1):
+            params["dilation"] = (dh, dw)
         self.ops.append(PlanOp("conv2d", inputs, [y], params))
         if out_name != out:
             self.by_name[out] = y   # conv node's own tensor name -> fused out
+        if start is not nd:
+            self.by_name[f"{start.name}:0"] = y     # BatchToSpaceND's
 
     def _group_merge(self, G: int, Cg: int, Ng: int) -> int:
         """How many consecutive groups of a grouped conv become one
@@ -744,9 +855,10 @@ class _Lowerer:
         is already in k order. The op carries that (R,S,C*M) weight, a
         (C*M,) bias, rsc = (R,S,C) with C the INPUT channels, and a
         `mult` key only when M > 1 (the golden call templates pin the
-        M == 1 op's params, keys and order)."""
+        M == 1 op's params, keys and order). Dilation (_conv_geometry)
+        rides the same way, as a `dilation` key only when it is not
+        (1, 1), and needs M == 1: the atrous separable conv."""
         x_ref, w_ref = nd.input[0], nd.input[1]
-        x = self.tid(x_ref)
         if _attr_s(nd, "data_format", "NHWC") != "NHWC":
             raise PlanError("only NHWC DepthwiseConv2dNative supported")
         w = np.asarray(self.weight_of(w_ref), dtype=np.float32)  # [R,S,C,M]
@@ -754,32 +866,14 @@ class _Lowerer:
         if M < 1:
             raise PlanError(f"depth_multiplier {M} unsupported")
         K = Cin * M
-        dil = _attr_ints(nd, "dilations") or [1, 1, 1, 1]
-        if any(d != 1 for d in dil):
-            raise PlanError(f"dilated depthwise conv unsupported ({dil})")
-        strides = _attr_ints(nd, "strides") or [1, 1, 1, 1]
-        padding = _attr_s(nd, "padding", "SAME")
-        xs = self.tensors[x].shape
-        H, W = int(xs[1]), int(xs[2])
-        sh, sw = strides[1], strides[2]
-        if padding == "SAME":
-            Ho, Wo = math.ceil(H / sh), math.ceil(W / sw)
-            pad_h = max((Ho - 1) * sh + R - H, 0)
-            pad_w = max((Wo - 1) * sw + S - W, 0)
-            pads = (pad_h // 2, pad_h - pad_h // 2,
-                    pad_w // 2, pad_w - pad_w // 2)
-        elif padding == "VALID":
-            Ho, Wo = (H - R) // sh + 1, (W - S) // sw + 1
-            pads = (0, 0, 0, 0)
-        elif padding == "EXPLICIT":
-            ep = _attr_ints(nd, "explicit_paddings")
-            pads = (ep[2], ep[3], ep[4], ep[5])
-            Ho = (H + pads[0] + pads[1] - R) // sh + 1
-            Wo = (W + pads[2] + pads[3] - S) // sw + 1
-        else:
-            raise PlanError(f"depthwise padding {padding}")
+        x, (sh, sw), (dh, dw), pads, (H, W), (Ho, Wo), start = \
+            self._conv_geometry(nd, "depthwise conv", x_ref, R, S)
+        if (dh, dw) != (1, 1) and M > 1:
+            raise PlanError(
+                f"dilated depthwise conv {nd.name} with depth_multiplier "
+                f"{M} unsupported (dilation {(dh, dw)})")
 
-        bias, bn, residual, act, final = self._absorb_act_chain(nd)
+        bias, bn, residual, act, final = self._absorb_act_chain(start)
         if bn is not None:
             scale, offset, mean, var, eps = bn
             g_ = scale / np.sqrt(var + eps)
@@ -803,6 +897,8 @@ class _Lowerer:
                   "hw": (H, W), "out_hw": (Ho, Wo)}
         if M > 1:
             params["mult"] = M
+        if (dh, dw) != (1, 1):
+            params["dilation"] = (dh, dw)
         self.ops.append(PlanOp("depthwise_conv", [x, w_id, b_id], [y],
                                params))
         if residual is not None:
@@ -821,6 +917,8 @@ class _Lowerer:
                 y = y3
         if out_name != out:
             self.by_name[out] = y
+        if start is not nd:
+            self.by_name[f"{start.name}:0"] = y     # BatchToSpaceND's
 
     def try_fold_int(self, nd: g.NodeDef, out: str) -> bool:
         """Fold StridedSlice / Pack / Mul / Add / Sub over integer

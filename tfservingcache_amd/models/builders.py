@@ -705,6 +705,128 @@ def build_unet(image_size=64, in_ch=3, base=16, num_classes=4,
 
 
 # ---------------------------------------------------------------------------
+# DeepLab v3 (inference), small: a strided stem, a residual block around a
+# dilated 3x3 conv, an atrous separable conv, ASPP with an image-pooling
+# branch, and a bilinear resize back to the input. The dilated-conv model
+# family: both spellings of a dilation that TF exports carry, the
+# `dilations` attribute (TF2/Keras) and the SpaceToBatchND / conv /
+# BatchToSpaceND sandwich (TF1/slim, every dilated depthwise conv).
+# ---------------------------------------------------------------------------
+def build_deeplab(image_size=65, num_classes=5, base=64, aspp_ch=32,
+                  rates=(6, 12, 18), seed=0):
+    """The stem is 3x3/s2 (feature map f = ceil(image_size / 2)), `base`
+    channels (a multiple of 64) run through the backbone and into the
+    ASPP, whose dilated branches use `rates`: large against f by default,
+    so most of their outer taps fall outside the map."""
+    if base % 64 or aspp_ch % 8:
+        raise ValueError("base must be a multiple of 64, aspp_ch of 8")
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+    i32 = gb.a_type(3)
+
+    def ints(name, v):
+        return gb.const(name, np.asarray(v, dtype=np.int32))
+
+    def bn(name, x, c, relu=True):
+        scale = gb.const(f"{name}/gamma",
+                         np.abs(rng.standard_normal(c)).astype(np.float32)
+                         * 0.5 + 0.5)
+        offset = gb.const(f"{name}/beta",
+                          (rng.standard_normal(c) * 0.1).astype(np.float32))
+        mean = gb.const(f"{name}/mean",
+                        (rng.standard_normal(c) * 0.1).astype(np.float32))
+        var = gb.const(f"{name}/var",
+                       np.abs(rng.standard_normal(c)).astype(np.float32)
+                       * 0.5 + 0.5)
+        h = gb.node("FusedBatchNormV3", f"{name}/bn",
+                    [x, scale, offset, mean, var], T=f32, U=f32,
+                    epsilon=gb.a_float(1e-3),
+                    is_training=gb.a_bool(False),
+                    data_format=gb.a_str("NHWC"))
+        return gb.node("Relu", f"{name}/relu", [h], T=f32) if relu else h
+
+    def conv(name, x, cin, cout, k=3, stride=1, rate=1, relu=True):
+        w = gb.const(f"{name}/w", (rng.standard_normal((k, k, cin, cout))
+                                   * np.sqrt(2.0 / (k * k * cin))
+                                   ).astype(np.float32))
+        attrs = {}
+        if rate > 1:
+            attrs["dilations"] = gb.a_ints([1, rate, rate, 1])
+        c = gb.node("Conv2D", f"{name}/conv", [x, w], T=f32,
+                    strides=gb.a_ints([1, stride, stride, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NHWC"), **attrs)
+        return bn(name, c, cout, relu)
+
+    def atrous_depthwise(name, x, c, hw, rate):
+        # tf.nn.depthwise_conv2d(x, w, [1,1,1,1], "SAME", rate): pad so the
+        # padded size is a multiple of the rate, VALID on each phase, crop
+        w = gb.const(f"{name}/w", (rng.standard_normal((3, 3, c, 1))
+                                   * np.sqrt(2.0 / 9)).astype(np.float32))
+        extra = -(hw + 2 * rate) % rate
+        pads = [[rate, rate + extra]] * 2
+        h = gb.node("SpaceToBatchND", f"{name}/s2b",
+                    [x, ints(f"{name}/block", [rate, rate]),
+                     ints(f"{name}/paddings", pads)],
+                    T=f32, Tblock_shape=i32, Tpaddings=i32)
+        h = gb.node("DepthwiseConv2dNative", f"{name}/depthwise", [h, w],
+                    T=f32, strides=gb.a_ints([1, 1, 1, 1]),
+                    padding=gb.a_str("VALID"), data_format=gb.a_str("NHWC"))
+        h = gb.node("BatchToSpaceND", f"{name}/b2s",
+                    [h, ints(f"{name}/block2", [rate, rate]),
+                     ints(f"{name}/crops", [[0, extra]] * 2)],
+                    T=f32, Tblock_shape=i32, Tcrops=i32)
+        return bn(name, h, c)
+
+    s = image_size
+    f = (s + 1) // 2
+    x = gb.placeholder("input", np.float32, [-1, s, s, 3],
+                       signature_name="input")
+    h = conv("stem", x, 3, base, stride=2)                      # f x f
+    # residual block, its 3x3 at dilation 2
+    r = conv("block/reduce", h, base, base // 2, k=1)
+    r = conv("block/atrous", r, base // 2, base // 2, rate=2)
+    r = conv("block/expand", r, base // 2, base, k=1, relu=False)
+    h = gb.node("Relu", "block/out",
+                [gb.node("AddV2", "block/add", [r, h], T=f32)], T=f32)
+    # atrous separable conv: sandwich-spelt depthwise + pointwise
+    h = atrous_depthwise("sep/dw", h, base, f, 2)
+    h = conv("sep/pw", h, base, base, k=1)
+    # ASPP
+    branches = [conv("aspp/b0", h, base, aspp_ch, k=1)]
+    for i, rate in enumerate(rates):
+        branches.append(conv(f"aspp/b{i + 1}", h, base, aspp_ch, rate=rate))
+    pooled = gb.node("Mean", "aspp/pool", [h, ints("aspp/pool/axes", [1, 2])],
+                     T=f32, Tidx=i32, keep_dims=gb.a_bool(True))
+    pooled = conv("aspp/image", pooled, base, aspp_ch, k=1)
+    branches.append(gb.node(
+        "ResizeBilinear", "aspp/image/resize",
+        [pooled, ints("aspp/image/size", [f, f])], T=f32,
+        align_corners=gb.a_bool(True), half_pixel_centers=gb.a_bool(False)))
+    cat = gb.node("ConcatV2", "aspp/concat",
+                  branches + [gb.const("aspp/axis", np.int32(3))], T=f32,
+                  N=gb.a_int(len(branches)), Tidx=i32)
+    h = conv("aspp/project", cat, aspp_ch * len(branches), base, k=1)
+    wh = gb.const("head/w", (rng.standard_normal((1, 1, base, num_classes))
+                             * np.sqrt(1.0 / base)).astype(np.float32))
+    bh = gb.const("head/b", np.zeros(num_classes, dtype=np.float32))
+    logits = gb.node("Conv2D", "head/conv", [h, wh], T=f32,
+                     strides=gb.a_ints([1, 1, 1, 1]),
+                     padding=gb.a_str("SAME"),
+                     data_format=gb.a_str("NHWC"))
+    logits = gb.node("BiasAdd", "head/logits", [logits, bh], T=f32)
+    logits = gb.node("ResizeBilinear", "logits",
+                     [logits, ints("logits/size", [s, s])], T=f32,
+                     align_corners=gb.a_bool(True),
+                     half_pixel_centers=gb.a_bool(False))
+    probs = gb.node("Softmax", "probs", [logits], T=f32)
+    gb.mark_output("probs", probs)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # BERT-base encoder (inference): embeddings -> 12 transformer layers ->
 # pooler. Frozen-graph decompositions for LayerNorm and GELU.
 # ---------------------------------------------------------------------------
