@@ -114,6 +114,16 @@ static void launch_call(const Call& c, hipStream_t s) {
       }
       break;
     case K_POOL:
+      // ints: [mode,N,H,W,C,Ho,Wo,kh,kw,sh,sw,pt,pl]; the 18-int form
+      // [mode,N,D,H,W,C,Do,Ho,Wo,kd,kh,kw,sd,sh,sw,pf,pt,pl] is a 3-D pool
+      if (I.size() == 18) {
+        launch_pool3d(s, cp(0), p(1), I[0] != 0, int(I[1]), int(I[2]),
+                      int(I[3]), int(I[4]), int(I[5]), int(I[6]), int(I[7]),
+                      int(I[8]), int(I[9]), int(I[10]), int(I[11]),
+                      int(I[12]), int(I[13]), int(I[14]), int(I[15]),
+                      int(I[16]), int(I[17]));
+        break;
+      }
       launch_pool(s, cp(0), p(1), I[0] != 0, int(I[1]), int(I[2]),
                   int(I[3]), int(I[4]), int(I[5]), int(I[6]), int(I[7]),
                   int(I[8]), int(I[9]), int(I[10]), int(I[11]), int(I[12]));
@@ -155,7 +165,19 @@ static void launch_call(const Call& c, hipStream_t s) {
       // ints: [N,H,W,C,Kc,R,S,sh,sw,pt,pl,Ho,Wo,k_pad,act(,groups
       // (,dh,dw))]; the 15-int form is a dense conv, the 18-int form a
       // dilated one (groups written as 1)
+      // The 23-int form [..15 as above.., groups, dh, dw (all 1),
+      // D, T, sd, pf, Do] is a 3-D conv on [N,D,H,W,C]
       const ushort* res = c.ptrs[3] ? cp(3) : nullptr;
+      if (I.size() == 23) {
+        launch_conv3d_igemm(s, cp(0), cp(1), cp(2), res, cp(4), p(5),
+                            int(I[0]), int(I[18]), int(I[1]), int(I[2]),
+                            int(I[3]), int(I[4]), int(I[19]), int(I[5]),
+                            int(I[6]), int(I[20]), int(I[7]), int(I[8]),
+                            int(I[21]), int(I[9]), int(I[10]), int(I[22]),
+                            int(I[11]), int(I[12]), int(I[13]), int(I[14]),
+                            int(I[15]), int(I[16]), int(I[17]));
+        break;
+      }
       launch_conv_igemm(s, cp(0), cp(1), cp(2), res, cp(4), p(5),
                         int(I[0]), int(I[1]), int(I[2]), int(I[3]),
                         int(I[4]), int(I[5]), int(I[6]), int(I[7]),

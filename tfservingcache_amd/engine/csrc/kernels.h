@@ -52,6 +52,15 @@ void launch_reduce_mean_mid(hipStream_t s, const ushort* x, ushort* y,
 void launch_pool(hipStream_t s, const ushort* x, ushort* y, bool is_max,
                  int N, int H, int W, int C, int Ho, int Wo, int kh, int kw,
                  int sh, int sw, int pt, int pl);
+// NDHWC max / average pooling (K_POOL's 18-int form). Taps outside the
+// volume are skipped; the average divides by the in-volume tap count. 8
+// channels per thread with 16-byte accesses when C % 8 == 0 and both
+// pointers are 16-byte aligned, one element per thread otherwise. Throws
+// before any launch on an extent, window or stride < 1.
+void launch_pool3d(hipStream_t s, const ushort* x, ushort* y, bool is_max,
+                   int N, int D, int H, int W, int C, int Do, int Ho, int Wo,
+                   int kd, int kh, int kw, int sd, int sh, int sw, int pf,
+                   int pt, int pl);
 void launch_transpose(hipStream_t s, const ushort* x, ushort* y, int ndim,
                       const int64_t* out_dims, const int64_t* in_strides,
                       int64_t n_out);
@@ -159,6 +168,22 @@ void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        int sh, int sw, int pt, int pl, int Ho, int Wo,
                        int k_pad, int act, int groups = 1, int dh = 1,
                        int dw = 1);
+// 3-D conv (K_CONV's 23-int form), NDHWC: y[N,Do,Ho,Wo,Kc] =
+// act(conv3d(x[N,D,H,W,C], w) + bias [+ residual]); tap (t, r, s) reads
+// di = do*sd - pf + t, hi = ho*sh - pt + r, wi = wo*sw - pl + s. w is
+// [Kc][pad64(T*R*S*C)] with k = ((t*R + r)*S + s)*C + c and
+// k_pad = pad64(T*R*S*C). Implicit GEMM on its own kernel, no im2col
+// buffer; C % 64 == 0 takes the instantiation whose tap is block-uniform.
+// groups, dh and dw are the 23-int form's reserved slots: throws before
+// any launch unless they are all 1, on C % 8 != 0, on a k_pad that is not
+// pad64(T*R*S*C), and on any extent or stride < 1.
+void launch_conv3d_igemm(hipStream_t s, const ushort* x, const ushort* w,
+                         const ushort* bias, const ushort* residual,
+                         const ushort* zeros, ushort* y,
+                         int N, int D, int H, int W, int C, int Kc,
+                         int T, int R, int S, int sd, int sh, int sw,
+                         int pf, int pt, int pl, int Do, int Ho, int Wo,
+                         int k_pad, int act, int groups, int dh, int dw);
 // dead-tap skipping of the dilated kernel: 0 never, 1 where it pays
 // (default: more than one block per CU and a filter reach of at least an
 // eighth of the image), 2 wherever C % 64 == 0. A measurement switch

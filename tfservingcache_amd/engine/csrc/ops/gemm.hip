@@ -1054,6 +1054,287 @@ void launch_conv_igemm(hipStream_t s, const ushort* x, const ushort* w,
                        act, g, ntm);
 }
 
+// ---------------------------------------------------------------------------
+// 3-D implicit-GEMM conv (C3D / I3D / R(2+1)D video nets, 3-D U-Net):
+//   M = N*Do*Ho*Wo,  N = Kc,  K = pad64(T*R*S*C),  k = ((t*R + r)*S + s)*C + c
+//   di = do*sd - pf + t,  hi = ho*sh - pt + r,  wi = wo*sw - pl + s
+// Same anatomy as conv_igemm_kernel (128x128x64 tiles, four waves, 16-byte
+// glds staging with the XOR source swizzle, two LDS buffers, one barrier
+// per K tile, 16x16x32 bf16 MFMA inside s_setprio, an LDS-restaged
+// coalesced epilogue (epilogue_store_f32 below), XCD swizzle). The A
+// gather over three spatial axes has no division in the K loop:
+//  - rows: a lane stages the same four A rows in every K tile, so
+//    m -> (n, do, ho, wo) is decomposed once. A row keeps the corner of
+//    its receptive field (di0, hi0, wi0) and `org`, the 64-bit element
+//    offset of that corner in x (it may lie in the padding and be
+//    negative; it is only ever added to an in-volume tap).
+//  - k: a lane's 8-channel chunk advances by exactly 64 in k per tile, so
+//    its (t, r, s, c) is a cursor advanced by add-and-carry. `koff`, the
+//    chunk's element offset from a row's corner, ((t*H + r)*W + s)*C + c,
+//    is the same for every row; it moves by 64 per tile plus a jump of
+//    (W - S)*C when s wraps into r and (H - R)*W*C when r wraps into t.
+//    A chunk's address is org + koff: one 64-bit add per row.
+//  - TAP_UNIFORM (C % 64 == 0): a K tile lies inside one tap, so
+//    (t, r, s), the tile's channel base and koff are block-uniform and
+//    live in scalar registers; the lane adds its chunk's 8*chunk_src. K
+//    has no pad tile then.
+// Chunks outside the volume, and the k >= T*R*S*C tail (t >= T), read the
+// zero page, so the four glds of a tile issue unconditionally.
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                   \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+struct Conv3dGeom {
+  int D, H, W, C, T, R, S, sd, sh, sw, pf, pt, pl, Do, Ho, Wo;
+};
+
+// epilogue_store rounds acc + bias to bf16 in its staging tile and rounds
+// again after the residual add and the activation: with a residual the
+// error reaches two bf16 roundings of the pre-residual value, which can
+// exceed 2^-8 * max|y|. This variant of it rounds once. The 128x128 tile's
+// four waves restage their 64x64 tiles as f32 - 16 KB each, exactly the
+// 64 KB of tile buffers, dead by now - and the stream-out pass (the same
+// 16-byte lanes, residual read coalesced) adds the residual, applies the
+// activation and rounds.
+template <bool HAS_RES>
+TFSC_DEV void epilogue_store_f32(f32x4_t (&acc)[4][4], char* smem,
+                                 const ushort* __restrict__ bias,
+                                 const ushort* __restrict__ residual,
+                                 ushort* __restrict__ Cb,
+                                 int M, int N, int m0, int n0, int wave,
+                                 int lane, int wm, int wn, int act) {
+  __syncthreads();              // tiles are dead; reuse as staging
+  float* stage = reinterpret_cast<float*>(smem + wave * 16384);
+  const int col_in = lane & 15;
+  const int row_base = (lane >> 4) * 4;
+  #pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+    #pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      int col = ni * 16 + col_in;
+      float bv = bf2f(bias[n0 + wn * 64 + col]);
+      #pragma unroll
+      for (int r = 0; r < 4; ++r)
+        stage[(mi * 16 + row_base + r) * 64 + col] = acc[mi][ni][r] + bv;
+    }
+  }
+  __syncthreads();
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    int chunk_id = i * 64 + lane;
+    int row = chunk_id >> 3;
+    int chunk = chunk_id & 7;
+    int grow = m0 + wm * 64 + row;
+    int gcol0 = n0 + wn * 64 + chunk * 8;
+    if (grow >= M) continue;
+    const f32x4_t* sp =
+        reinterpret_cast<const f32x4_t*>(stage + row * 64 + chunk * 8);
+    f32x4_t lo = sp[0], hi = sp[1];
+    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    int64_t goff = (int64_t)grow * N + gcol0;
+    const bool full = gcol0 + 7 < N;
+    if (HAS_RES) {
+      if (full) {
+        bf16x8 rv = *reinterpret_cast<const bf16x8*>(residual + goff);
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += bf2f((ushort)rv[j]);
+      } else {
+        for (int j = 0; j < 8 && gcol0 + j < N; ++j)
+          v[j] += bf2f(residual[goff + j]);
+      }
+    }
+    bf16x8 o;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (short)f2bf(act_apply(v[j], act));
+    if (full) {
+      *reinterpret_cast<bf16x8*>(Cb + goff) = o;
+    } else {
+      for (int j = 0; j < 8 && gcol0 + j < N; ++j)
+        Cb[goff + j] = (ushort)o[j];
+    }
+  }
+}
+
+template <bool HAS_RES, bool TAP_UNIFORM>
+__global__ __launch_bounds__(THREADS)
+void conv3d_igemm_kernel(const ushort* __restrict__ x,
+                         const ushort* __restrict__ B,
+                         const ushort* __restrict__ bias,
+                         const ushort* __restrict__ residual,
+                         const ushort* __restrict__ zeros,
+                         ushort* __restrict__ Cout,
+                         int M, int N, int K, int act, Conv3dGeom g,
+                         int n_tiles_m) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * BM * BK * 2];
+  auto lds_a = [&](int buf) -> char* { return smem + buf * 32768; };
+  auto lds_b = [&](int buf) -> char* { return smem + 16384 + buf * 32768; };
+
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int tile_m = bid % n_tiles_m;
+  const int tile_n = bid / n_tiles_m;
+  const int m0 = tile_m * BM;
+  const int n0 = tile_n * BN;
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r_in = lane >> 3;
+  const int chunk_src = (lane & 7) ^ r_in;    // row & 7 == r_in
+
+  // the lane's four A rows: receptive-field corner and its offset in x
+  int di0[4], hi0[4], wi0[4];
+  int64_t org[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int m = m0 + wave * 32 + i * 8 + r_in;
+    m = m < M - 1 ? m : M - 1;
+    int wo = m % g.Wo;
+    int q = m / g.Wo;
+    int ho = q % g.Ho;
+    q /= g.Ho;
+    int n = q / g.Do;
+    di0[i] = (q % g.Do) * g.sd - g.pf;
+    hi0[i] = ho * g.sh - g.pt;
+    wi0[i] = wo * g.sw - g.pl;
+    org[i] = ((((int64_t)n * g.D + di0[i]) * g.H + hi0[i]) * g.W + wi0[i]) *
+             g.C;
+  }
+
+  // the k cursor: tap (kt, kr, ks) and channel kc of the lane's chunk
+  // (TAP_UNIFORM: of the tile's first chunk), koff as above
+  int kt = 0, kr = 0, ks = 0, kc = 0;
+  if (!TAP_UNIFORM) {
+    int k = chunk_src * 8;
+    kc = k % g.C;
+    int q = k / g.C;
+    ks = q % g.S;
+    q /= g.S;
+    kr = q % g.R;
+    kt = q / g.R;
+  }
+  int64_t koff = (((int64_t)kt * g.H + kr) * g.W + ks) * g.C + kc;
+  const int64_t r_jump = (int64_t)(g.W - g.S) * g.C;
+  const int64_t t_jump = (int64_t)(g.H - g.R) * g.W * g.C;
+
+  // stage the K tile the cursor stands on (k0 is its first k), then step
+  auto stage = [&](int k0, int buf) {
+    const int64_t off = TAP_UNIFORM ? koff + chunk_src * 8 : koff;
+    const bool k_ok = TAP_UNIFORM || kt < g.T;
+    char* lds_tile = lds_a(buf);
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned di = unsigned(di0[q] + kt);    // negative wraps above D
+      unsigned hi = unsigned(hi0[q] + kr);
+      unsigned wi = unsigned(wi0[q] + ks);
+      bool ok = k_ok & (di < unsigned(g.D)) & (hi < unsigned(g.H)) &
+                (wi < unsigned(g.W));
+      const ushort* gptr = ok ? x + (org[q] + off) : zeros;
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const uint32_t*>(gptr),
+          reinterpret_cast<uint32_t*>(lds_tile + (wave * 32 + q * 8) * 128),
+          16, 0, 0);
+    }
+    stage_tile_glds<128, 4>(B, K, N - 1, n0, k0, lds_b(buf), wave, lane);
+    kc += BK;
+    koff += BK;
+    while (kc >= g.C) {                       // C >= 64: at most once
+      kc -= g.C;
+      if (++ks == g.S) {
+        ks = 0;
+        koff += r_jump;
+        if (++kr == g.R) {
+          kr = 0;
+          koff += t_jump;
+          ++kt;
+        }
+      }
+    }
+  };
+
+  f32x4_t acc[4][4] = {};
+  const int n_ktiles = K / BK;
+
+  stage(0, 0);
+
+  int cur = 0;
+  for (int i = 0; i < n_ktiles; ++i) {
+    __syncthreads();
+    if (i + 1 < n_ktiles) stage((i + 1) * BK, cur ^ 1);
+    const char* at = lds_a(cur);
+    const char* bt = lds_b(cur);
+    const int frow = lane & 15;
+    const int kgrp = lane >> 4;
+    #pragma unroll
+    for (int kstep = 0; kstep < 2; ++kstep) {
+      bf16x8_t a_frag[4], b_frag[4];
+      const int chunk = kstep * 4 + kgrp;
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        a_frag[mi] = *reinterpret_cast<const bf16x8_t*>(
+            at + lds_off(wm * 64 + mi * 16 + frow, chunk));
+      #pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+        b_frag[ni] = *reinterpret_cast<const bf16x8_t*>(
+            bt + lds_off(wn * 64 + ni * 16 + frow, chunk));
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_frag[mi], b_frag[ni], acc[mi][ni], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    cur ^= 1;
+  }
+
+  epilogue_store_f32<HAS_RES>(acc, smem, bias, residual, Cout, M, N, m0, n0,
+                              wave, lane, wm, wn, act);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+void launch_conv3d_igemm(hipStream_t s, const ushort* x, const ushort* w,
+                         const ushort* bias, const ushort* residual,
+                         const ushort* zeros, ushort* y,
+                         int N_img, int D, int H, int W, int C, int Kc,
+                         int T, int R, int S, int sd, int sh, int sw,
+                         int pf, int pt, int pl, int Do, int Ho, int Wo,
+                         int k_pad, int act, int groups, int dh, int dw) {
+  if (groups != 1)
+    throw std::runtime_error("grouped conv3d_igemm unsupported");
+  if (dh != 1 || dw != 1)
+    throw std::runtime_error("dilated conv3d_igemm unsupported");
+  if (D < 1 || T < 1 || sd < 1 || Do < 1)
+    throw std::runtime_error("conv3d_igemm: D, T, sd and Do must be >= 1");
+  if (N_img < 1 || H < 1 || W < 1 || C < 1 || Kc < 1 || R < 1 || S < 1 ||
+      sh < 1 || sw < 1 || Ho < 1 || Wo < 1)
+    throw std::runtime_error(
+        "conv3d_igemm: every extent and stride must be >= 1");
+  if (C % 8 != 0)
+    throw std::runtime_error("conv3d_igemm requires C % 8 == 0");
+  int64_t trsc = (int64_t)T * R * S * C;
+  if (trsc > INT32_MAX - BK || k_pad != (trsc + BK - 1) / BK * BK)
+    throw std::runtime_error("conv3d_igemm k_pad must be pad64(T*R*S*C)");
+  int64_t M = (int64_t)N_img * Do * Ho * Wo;
+  if (M > INT32_MAX - BM)
+    throw std::runtime_error("conv3d_igemm: more than 2^31 output voxels");
+  Conv3dGeom g{D, H, W, C, T, R, S, sd, sh, sw, pf, pt, pl, Do, Ho, Wo};
+  int ntm = int(ceil_div(M, BM)), ntn = int(ceil_div(Kc, BN));
+  dim3 grid(ntm * ntn);
+  bool uni = C % BK == 0;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, x, w, bias, residual,
+                       zeros, y, int(M), Kc, k_pad, act, g, ntm);
+  };
+  if (residual && uni) launch(conv3d_igemm_kernel<true, true>);
+  else if (residual)   launch(conv3d_igemm_kernel<true, false>);
+  else if (uni)        launch(conv3d_igemm_kernel<false, true>);
+  else                 launch(conv3d_igemm_kernel<false, false>);
+}
+
 void launch_batched_gemm(hipStream_t s, const ushort* A, const ushort* B,
                          ushort* C, int64_t bat, int64_t M, int64_t N,
                          int64_t K, int64_t strideA, int64_t strideB,

@@ -1369,4 +1369,154 @@ void launch_zero_insert_nhwc(hipStream_t s, const ushort* x, ushort* y,
                      x, y, N, h, w, C, sh, sw, Ho, Wo);
 }
 
+// ---------------------------------------------------------------------------
+// 3-D pooling (NDHWC; MaxPool3D / AvgPool3D). Same split as the 2-D pair:
+// one thread per 8 channels of one output voxel with 16-byte loads and
+// stores, one thread per element otherwise; grid-stride, 64-bit offsets.
+// The window is clipped to the volume per axis before the tap loops, so a
+// tap outside the volume is never read and the average's divisor (TF
+// excludes padding) is the product of the three clipped extents. Max
+// starts from -inf; the average is summed and divided in f32 and rounded
+// once.
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                   \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+struct Pool3dGeom {
+  int N, D, H, W, C, Do, Ho, Wo, kd, kh, kw, sd, sh, sw, pf, pt, pl;
+};
+
+// [lo, hi) of the taps of a window starting at i0 that lie inside [0, n);
+// empty (hi == lo) when the window misses the axis altogether
+TFSC_DEV void pool_clip(int i0, int k, int n, int& lo, int& hi) {
+  lo = i0 < 0 ? -i0 : 0;
+  hi = n - i0 < k ? n - i0 : k;
+  hi = hi < lo ? lo : hi;
+}
+
+template <bool IS_MAX>
+__global__ void k_pool3d_v8(const ushort* __restrict__ x,
+                            ushort* __restrict__ y, Pool3dGeom g) {
+  int c8 = g.C >> 3;
+  int64_t n_grp = (int64_t)g.N * g.Do * g.Ho * g.Wo * c8;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_grp; i += stride) {
+    int grp = int(i % c8);
+    int64_t t = i / c8;
+    int wo = int(t % g.Wo); t /= g.Wo;
+    int ho = int(t % g.Ho); t /= g.Ho;
+    int dz = int(t % g.Do); int n = int(t / g.Do);
+    int d0 = dz * g.sd - g.pf, h0 = ho * g.sh - g.pt, w0 = wo * g.sw - g.pl;
+    int dlo, dhi, hlo, hhi, wlo, whi;
+    pool_clip(d0, g.kd, g.D, dlo, dhi);
+    pool_clip(h0, g.kh, g.H, hlo, hhi);
+    pool_clip(w0, g.kw, g.W, wlo, whi);
+    float acc[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = IS_MAX ? -INFINITY : 0.f;
+    const ushort* img = x + (int64_t)n * g.D * g.H * g.W * g.C + grp * 8;
+    for (int a = dlo; a < dhi; ++a) {
+      for (int b = hlo; b < hhi; ++b) {
+        const ushort* row =
+            img + (((int64_t)(d0 + a) * g.H + (h0 + b)) * g.W + w0) * g.C;
+        for (int q = wlo; q < whi; ++q) {
+          uint4 v = *reinterpret_cast<const uint4*>(row + (int64_t)q * g.C);
+          uint32_t u[4] = {v.x, v.y, v.z, v.w};
+          #pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float lo = bf_lo(u[j]), hi = bf_hi(u[j]);
+            if (IS_MAX) {
+              acc[2 * j] = fmaxf(acc[2 * j], lo);
+              acc[2 * j + 1] = fmaxf(acc[2 * j + 1], hi);
+            } else {
+              acc[2 * j] += lo;
+              acc[2 * j + 1] += hi;
+            }
+          }
+        }
+      }
+    }
+    if (!IS_MAX) {
+      int cnt = (dhi - dlo) * (hhi - hlo) * (whi - wlo);
+      float div = cnt > 0 ? float(cnt) : 1.f;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] /= div;
+    }
+    uint4 out;
+    out.x = f2bf2(acc[0], acc[1]);
+    out.y = f2bf2(acc[2], acc[3]);
+    out.z = f2bf2(acc[4], acc[5]);
+    out.w = f2bf2(acc[6], acc[7]);
+    *reinterpret_cast<uint4*>(y + i * 8) = out;
+  }
+}
+
+template <bool IS_MAX>
+__global__ void k_pool3d(const ushort* __restrict__ x,
+                         ushort* __restrict__ y, Pool3dGeom g) {
+  int64_t n_out = (int64_t)g.N * g.Do * g.Ho * g.Wo * g.C;
+  int64_t i0 = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TPB;
+  for (int64_t i = i0; i < n_out; i += stride) {
+    int c = int(i % g.C);
+    int64_t t = i / g.C;
+    int wo = int(t % g.Wo); t /= g.Wo;
+    int ho = int(t % g.Ho); t /= g.Ho;
+    int dz = int(t % g.Do); int n = int(t / g.Do);
+    int d0 = dz * g.sd - g.pf, h0 = ho * g.sh - g.pt, w0 = wo * g.sw - g.pl;
+    int dlo, dhi, hlo, hhi, wlo, whi;
+    pool_clip(d0, g.kd, g.D, dlo, dhi);
+    pool_clip(h0, g.kh, g.H, hlo, hhi);
+    pool_clip(w0, g.kw, g.W, wlo, whi);
+    float acc = IS_MAX ? -INFINITY : 0.f;
+    const ushort* img = x + (int64_t)n * g.D * g.H * g.W * g.C + c;
+    for (int a = dlo; a < dhi; ++a) {
+      for (int b = hlo; b < hhi; ++b) {
+        const ushort* row =
+            img + (((int64_t)(d0 + a) * g.H + (h0 + b)) * g.W + w0) * g.C;
+        for (int q = wlo; q < whi; ++q) {
+          float v = bf2f(row[(int64_t)q * g.C]);
+          acc = IS_MAX ? fmaxf(acc, v) : acc + v;
+        }
+      }
+    }
+    if (!IS_MAX) {
+      int cnt = (dhi - dlo) * (hhi - hlo) * (whi - wlo);
+      acc /= cnt > 0 ? float(cnt) : 1.f;
+    }
+    y[i] = f2bf(acc);
+  }
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+void launch_pool3d(hipStream_t s, const ushort* x, ushort* y, bool is_max,
+                   int N, int D, int H, int W, int C, int Do, int Ho, int Wo,
+                   int kd, int kh, int kw, int sd, int sh, int sw, int pf,
+                   int pt, int pl) {
+  if (N < 1 || D < 1 || H < 1 || W < 1 || C < 1 || Do < 1 || Ho < 1 ||
+      Wo < 1 || kd < 1 || kh < 1 || kw < 1 || sd < 1 || sh < 1 || sw < 1)
+    throw std::runtime_error(
+        "pool3d: every extent, window and stride must be >= 1");
+  Pool3dGeom g{N, D, H, W, C, Do, Ho, Wo, kd, kh, kw, sd, sh, sw, pf, pt, pl};
+  int64_t n_out = (int64_t)N * Do * Ho * Wo * C;
+  if (C % 8 == 0 && aligned16(x, y)) {
+    dim3 grid(grid_for(n_out / 8));
+    if (is_max)
+      hipLaunchKernelGGL(k_pool3d_v8<true>, grid, dim3(TPB), 0, s, x, y, g);
+    else
+      hipLaunchKernelGGL(k_pool3d_v8<false>, grid, dim3(TPB), 0, s, x, y, g);
+    return;
+  }
+  dim3 grid(grid_for(n_out));
+  if (is_max)
+    hipLaunchKernelGGL(k_pool3d<true>, grid, dim3(TPB), 0, s, x, y, g);
+  else
+    hipLaunchKernelGGL(k_pool3d<false>, grid, dim3(TPB), 0, s, x, y, g);
+}
+
 }  // namespace tfsc

@@ -282,6 +282,12 @@ class _Emitter:
                     H, W = op.params["hw"]
                     c8 = (Cin + 7) // 8 * 8
                     scratch_sizes[oi] = self.batch * H * W * c8 * 2
+            if op.kind == "conv3d":
+                # the same channel-pad scratch, over N*D*H*W rows
+                Cin = op.params["trsck"][3]
+                if Cin % 8 != 0:
+                    rows = _numel(self.shapes[op.inputs[0]][:-1])
+                    scratch_sizes[oi] = rows * ((Cin + 7) // 8 * 8) * 2
             if op.kind == "topk_last":
                 # a split row's partial results: P lists of k 64-bit
                 # composites per row
@@ -408,6 +414,8 @@ class _Emitter:
                 self._c_gemm(op, oi)
             elif k == "conv2d":
                 self._c_conv(op, oi)
+            elif k == "conv3d":
+                self._c_conv3d(op, oi)
             elif k == "batched_gemm":
                 self._c_bgemm(op)
             elif k == "attention":
@@ -475,6 +483,14 @@ class _Emitter:
                 call("POOL", io(op, 1),
                      [1 if p["mode"] == "max" else 0,
                       n, h, w, c, ho, wo, kh, kw, sh, sw, pt, pl])
+            elif k == "pool3d":
+                # POOL's 18-int form
+                n, d, h, w, c = xs
+                do, ho, wo = p["out_dhw"]
+                pf, _pk, pt, _pb, pl, _pr = p["pads"]
+                call("POOL", io(op, 1),
+                     [1 if p["mode"] == "max" else 0, n, d, h, w, c,
+                      do, ho, wo, *p["ksize"], *p["stride"], pf, pt, pl])
             elif k == "resize":
                 n, h, w, c = xs
                 ho, wo = p["out_hw"]
@@ -717,6 +733,50 @@ class _Emitter:
                         res, zeros, out],
                        [n, H, W, c8, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
                         _pad64(wR * wS * c8), act])
+
+    def _c_conv3d(self, op: PlanOp, oi: int) -> None:
+        """CONV's 23-int form: the 15 ints of a 2-D conv on the (H, W)
+        axes, groups / dh / dw written as 1, then [D, T, sd, pf, Do]. The
+        master weight is [T*R,S,C,K], so ("cw", idx) is
+        [Kc][pad64(T*R*S*C)] in (t,r,s,c) order. The 1x1x1 GEMM shortcut
+        and the C % 8 != 0 channel widening are the 2-D ones over
+        N*D*H*W rows."""
+        p = op.params
+        T, R, S, C, Kc = p["trsck"]
+        sd, sh, sw = p["stride"]
+        pf, pk, pt, pb, pl, pr = p["pads"]
+        Do, Ho, Wo = p["out_dhw"]
+        x, w_idx = op.inputs[0], op.inputs[1]
+        n, D, H, W, xC = self.shapes[x]
+        if self._weight_shape(w_idx) != (T * R, S, C, Kc) or xC != C:
+            raise KeyError(f"no [T*R,S,C,K] master weight for tensor {w_idx}")
+        bias = self._weight(op.inputs[2])
+        res = self._ptr(op.inputs[3]) if p.get("residual") else None
+        act = _act(p)
+        out = self._ptr(op.outputs[0])
+        zeros = (("zeros",), 0)
+
+        def ints(c):
+            return [n, H, W, c, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                    _pad64(T * R * S * c), act, 1, 1, 1, D, T, sd, pf, Do]
+
+        if (T, R, S) == (1, 1, 1) and (sd, sh, sw) == (1, 1, 1) and \
+                not any(p["pads"]) and C % 64 == 0:
+            self._call("GEMM",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res, out],
+                       [n * D * H * W, Kc, C, act], [1.0])
+        elif C % 8 == 0:
+            self._call("CONV",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res, zeros,
+                        out], ints(C))
+        else:
+            c8 = (C + 7) // 8 * 8
+            scratch = self._scratch(oi)
+            self._call("PAD_LAST", [self._ptr(x), scratch],
+                       [n * D * H * W, C, c8])
+            self._call("CONV",
+                       [scratch, (("cw", w_idx, "cpad", c8), 0), bias, res,
+                        zeros, out], ints(c8))
 
     def _c_bgemm(self, op: PlanOp) -> None:
         p = op.params

@@ -186,6 +186,10 @@ class CpuExecutor:
             self._depthwise(op, _get, vals)
         elif k == "pool":
             self._pool(op, _get, vals)
+        elif k == "conv3d":
+            self._conv3d(op, _get, vals)
+        elif k == "pool3d":
+            self._pool3d(op, _get, vals)
         elif k == "global_mean":
             x = _get(op.inputs[0])
             y = x.mean(axis=(1, 2), keepdims=p.get("keep", False))
@@ -375,6 +379,55 @@ class CpuExecutor:
         y = y + b
         vals[op.outputs[0]] = _act(y, p.get("act", "none")).astype(
             np.float32)
+
+    @staticmethod
+    def _windows3d(xp, window, stride, out_dhw):
+        """The strided [N,Do,Ho,Wo,C] view of the padded NDHWC volume xp
+        under each tap (a, b, c) of the window, in (a, b, c) order."""
+        (sd, sh, sw), (Do, Ho, Wo) = stride, out_dhw
+        for a in range(window[0]):
+            for b in range(window[1]):
+                for c in range(window[2]):
+                    yield xp[:, a:a + sd * Do:sd, b:b + sh * Ho:sh,
+                             c:c + sw * Wo:sw, :]
+
+    def _conv3d(self, op: PlanOp, _get, vals) -> None:
+        x = _get(op.inputs[0])          # [N,D,H,W,C]
+        w = _get(op.inputs[1])          # [T*R,S,C,K], k = ((t*R+r)*S+s)*C+c
+        b = _get(op.inputs[2])          # [K]
+        p = op.params
+        T, R, S, C, K = p["trsck"]
+        pf, pk, pt, pb, pl, pr = p["pads"]
+        Do, Ho, Wo = p["out_dhw"]
+        xp = np.pad(x, ((0, 0), (pf, pk), (pt, pb), (pl, pr), (0, 0)))
+        # im2col, one tap at a time
+        cols = np.empty((x.shape[0], Do, Ho, Wo, T * R * S * C),
+                        dtype=np.float32)
+        for i, patch in enumerate(self._windows3d(xp, (T, R, S), p["stride"],
+                                                  p["out_dhw"])):
+            cols[..., i * C:(i + 1) * C] = patch
+        y = cols.reshape(-1, T * R * S * C) @ w.reshape(-1, K)
+        y = y.reshape(x.shape[0], Do, Ho, Wo, K) + b
+        if p.get("residual"):
+            y = y + _get(op.inputs[3])
+        vals[op.outputs[0]] = _act(y, p.get("act", "none")).astype(np.float32)
+
+    def _pool3d(self, op: PlanOp, _get, vals) -> None:
+        x = _get(op.inputs[0])          # [N,D,H,W,C]
+        p = op.params
+        pf, pk, pt, pb, pl, pr = p["pads"]
+        pad = ((0, 0), (pf, pk), (pt, pb), (pl, pr), (0, 0))
+        geom = (p["ksize"], p["stride"], p["out_dhw"])
+        if p["mode"] == "max":
+            xp = np.pad(x, pad, constant_values=-np.inf)
+            out = np.maximum.reduce(list(self._windows3d(xp, *geom)))
+        else:
+            # padded cells are excluded from the divisor, as in _pool
+            ones = np.pad(np.ones((1,) + x.shape[1:4] + (1,), np.float32),
+                          pad)
+            out = sum(self._windows3d(np.pad(x, pad), *geom)) / \
+                np.maximum(sum(self._windows3d(ones, *geom)), 1.0)
+        vals[op.outputs[0]] = out.astype(np.float32)
 
     def _pool(self, op: PlanOp, _get, vals) -> None:
         x = _get(op.inputs[0])

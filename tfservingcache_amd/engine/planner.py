@@ -393,6 +393,12 @@ class _Lowerer:
         if op == "DepthwiseConv2dNative":
             self.lower_depthwise(nd, out)
             return
+        if op == "Conv3D":
+            self.lower_conv3d(nd, out)
+            return
+        if op in ("MaxPool3D", "AvgPool3D"):
+            self.lower_pool3d(nd, out)
+            return
         if op == "Einsum":
             self.lower_einsum(nd, out)
             return
@@ -594,7 +600,8 @@ class _Lowerer:
             elif nxt.op in ("FusedBatchNorm", "FusedBatchNormV3") and \
                     bn is None and residual is None and act == ACT_NONE and \
                     not _attr_b(nxt, "is_training", False) and \
-                    _attr_s(nxt, "data_format", "NHWC") == "NHWC" and \
+                    _attr_s(nxt, "data_format", "NHWC") in ("NHWC",
+                                                            "NDHWC") and \
                     all(self.const_value(r) is not None for r in nxt.input[1:5]):
                 bn = tuple(np.asarray(self.weight_of(r), dtype=np.float32)
                            for r in nxt.input[1:5]) + \
@@ -832,6 +839,112 @@ class _Lowerer:
             self.by_name[out] = y   # conv node's own tensor name -> fused out
         if start is not nd:
             self.by_name[f"{start.name}:0"] = y     # BatchToSpaceND's
+
+    def _geometry3d(self, nd: g.NodeDef, who: str, window, stride_attr: str):
+        """(x tensor, (D,H,W,C), strides, six pads, (Do,Ho,Wo)) of a Conv3D
+        / MaxPool3D / AvgPool3D node on an NDHWC input whose D, H, W and C
+        are concrete. `window` is the filter's or pool's (kd, kh, kw).
+        SAME pads per axis as _conv_geometry does for 2-D: low half first,
+        the odd element after. TF defines SAME and VALID only here."""
+        if _attr_s(nd, "data_format", "NDHWC") != "NDHWC":
+            raise PlanError(f"{who}: only NDHWC supported (data_format "
+                            f"{_attr_s(nd, 'data_format')})")
+        x = self.tid(nd.input[0])
+        xs = self.tensors[x].shape                      # [B,D,H,W,C]
+        if len(xs) != 5 or any(is_sym(d) for d in xs[1:]):
+            raise PlanError(f"{who}: needs a [B,D,H,W,C] input with "
+                            f"concrete D, H, W and C (got {xs})")
+        st = _attr_ints(nd, stride_attr) or [1] * 5
+        if len(st) != 5 or st[0] != 1 or st[4] != 1 or min(st) < 1:
+            raise PlanError(f"{who}: batch or channel stride unsupported "
+                            f"({stride_attr} {st})")
+        padding = _attr_s(nd, "padding", "VALID")
+        if padding not in ("SAME", "VALID"):
+            raise PlanError(f"{who}: padding {padding}")
+        dims = tuple(int(d) for d in xs[1:4])
+        pads, outs = [], []
+        for size, k, s in zip(dims, window, st[1:4]):
+            if padding == "SAME":
+                o = math.ceil(size / s)
+                tot = max((o - 1) * s + k - size, 0)
+            else:
+                o, tot = (size - k) // s + 1, 0
+            if o < 1:
+                raise PlanError(f"{who}: window {tuple(window)} exceeds "
+                                f"the input {dims} (VALID)")
+            pads += [tot // 2, tot - tot // 2]
+            outs.append(o)
+        return x, dims + (int(xs[4]),), tuple(st[1:4]), tuple(pads), \
+            tuple(outs)
+
+    def lower_conv3d(self, nd: g.NodeDef, out: str) -> None:
+        """Conv3D (NDHWC, dilation 1, dense) with BiasAdd / BN / residual /
+        activation folded in -> one conv3d op on the 3-D implicit-GEMM
+        kernel. The filter [T,R,S,C,K] is stored as the rank-4 master
+        [T*R,S,C,K], a plain reshape: the conv weight transforms then give
+        [K][pad64(T*R*S*C)] in (t,r,s,c) order with no 3-D case. The op
+        carries trsck, stride (sd,sh,sw), six pads, dhw, out_dhw and act.
+        Dilated and grouped Conv3D and NCDHW are PlanErrors."""
+        who = f"Conv3D {nd.name}"
+        dil = _attr_ints(nd, "dilations") or [1] * 5
+        if any(d != 1 for d in dil):
+            raise PlanError(f"dilated {who} unsupported ({dil})")
+        w_v = self.const_value(nd.input[1])
+        if w_v is None or np.ndim(w_v) != 5:
+            raise PlanError(f"{who}: the filter {nd.input[1]} must be a "
+                            f"constant [T,R,S,C,K]")
+        w = np.asarray(w_v, dtype=np.float32)
+        T, R, S, Cin, K = w.shape
+        x, (D, H, W, C), stride, pads, out_dhw = self._geometry3d(
+            nd, who, (T, R, S), "strides")
+        if C != Cin:
+            raise PlanError(f"grouped {who} unsupported: input has {C} "
+                            f"channels, filter {w.shape} takes {Cin}")
+
+        bias, bn, residual, act, final = self._absorb_act_chain(nd)
+        if bn is not None:
+            scale, offset, mean, var, eps = bn
+            g_ = scale / np.sqrt(var + eps)
+            w = w * g_.reshape(1, 1, 1, 1, K)
+            base = bias if bias is not None else np.zeros(K, np.float32)
+            bias = (base - mean) * g_ + offset
+        if bias is None:
+            bias = np.zeros(K, np.float32)
+        w = w.reshape(T * R, S, Cin, K)
+        w_id = self.new_tensor(tuple(w.shape), "f32", "weight",
+                               f"{nd.name}/fused_w", weight=w)
+        b_id = self.new_tensor((K,), "f32", "weight",
+                               f"{nd.name}/fused_b", weight=bias)
+        out_name = f"{final.name}:0"
+        y = self.new_tensor((self.tensors[x].shape[0],) + out_dhw + (K,),
+                            "f32", "activation", out_name)
+        inputs = [x, w_id, b_id]
+        params = {"trsck": (T, R, S, Cin, K), "stride": stride,
+                  "pads": pads, "dhw": (D, H, W), "out_dhw": out_dhw,
+                  "act": act}
+        if residual is not None:
+            inputs.append(self.tid(residual))
+            params["residual"] = True
+        self.ops.append(PlanOp("conv3d", inputs, [y], params))
+        if out_name != out:
+            self.by_name[out] = y   # conv node's own tensor name -> fused out
+
+    def lower_pool3d(self, nd: g.NodeDef, out: str) -> None:
+        """MaxPool3D / AvgPool3D (NDHWC) -> one pool3d op. The average
+        excludes padding from the divisor, as the 2-D pool does."""
+        who = f"{nd.op} {nd.name}"
+        ks = _attr_ints(nd, "ksize")
+        if len(ks) != 5 or ks[0] != 1 or ks[4] != 1 or min(ks) < 1:
+            raise PlanError(f"{who}: batch or channel window unsupported "
+                            f"(ksize {ks})")
+        x, (D, H, W, C), stride, pads, out_dhw = self._geometry3d(
+            nd, who, ks[1:4], "strides")
+        y = self.new_tensor((self.tensors[x].shape[0],) + out_dhw + (C,),
+                            "f32", "activation", out)
+        self.ops.append(PlanOp("pool3d", [x], [y], {
+            "mode": "max" if nd.op == "MaxPool3D" else "avg",
+            "ksize": tuple(ks[1:4]), "stride": stride, "pads": pads,
+            "dhw": (D, H, W), "out_dhw": out_dhw}))
 
     def _group_merge(self, G: int, Cg: int, Ng: int) -> int:
         """How many consecutive groups of a grouped conv become one
@@ -1767,9 +1880,10 @@ class _Lowerer:
 
     def lower_batchnorm_standalone(self, nd: g.NodeDef, out: str) -> None:
         """FusedBatchNorm whose producer isn't a conv — lower to the fused
-        scale/shift (+ optional downstream relu) kernel."""
-        if _attr_s(nd, "data_format", "NHWC") != "NHWC":
-            raise PlanError("only NHWC FusedBatchNorm supported")
+        scale/shift (+ optional downstream relu) kernel. NDHWC (Keras on
+        rank-5 inputs) is per-channel over the last axis like NHWC."""
+        if _attr_s(nd, "data_format", "NHWC") not in ("NHWC", "NDHWC"):
+            raise PlanError("only NHWC / NDHWC FusedBatchNorm supported")
         x = self.tid(nd.input[0])
         scale, offset, mean, var = (np.asarray(self.weight_of(r),
                                                dtype=np.float32)

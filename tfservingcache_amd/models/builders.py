@@ -980,6 +980,86 @@ def build_bert(seq_len=128, hidden=768, layers=12, heads=12,
 
 
 # ---------------------------------------------------------------------------
+# Video ResNet (NDHWC, inference): the 3-D conv family in one small graph,
+# as Keras exports it (Conv3D + FusedBatchNormV3 with data_format NDHWC).
+# An RGB [3,7,7]/(1,2,2) stem, MaxPool3D [1,3,3]/(1,2,2), a basic residual
+# block of two 3x3x3 convs (R3D), an R(2+1)D block ([1,3,3] then [3,1,1]),
+# a stage with temporal and spatial stride 2 behind a 1x1x1 stride-2
+# shortcut, a 1x1x1 head conv, AvgPool3D, GlobalAveragePooling3D (Mean over
+# [1,2,3]), dense, softmax.
+# ---------------------------------------------------------------------------
+def build_video_resnet(frames=8, image_size=32, num_classes=10, seed=0,
+                       width=32):
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32 = gb.a_type(1)
+
+    def conv(name, x, cin, cout, k, stride=(1, 1, 1), use_relu=True,
+             add_to=None):
+        w = gb.const(f"{name}/w", (rng.standard_normal((*k, cin, cout))
+                                   * np.sqrt(2.0 / (np.prod(k) * cin))
+                                   ).astype(np.float32))
+        c = gb.node("Conv3D", f"{name}/conv", [x, w], T=f32,
+                    strides=gb.a_ints([1, *stride, 1]),
+                    padding=gb.a_str("SAME"),
+                    data_format=gb.a_str("NDHWC"))
+        stats = [gb.const(f"{name}/{n}", v.astype(np.float32)) for n, v in (
+            ("gamma", np.abs(rng.standard_normal(cout)) * 0.5 + 0.5),
+            ("beta", rng.standard_normal(cout) * 0.1),
+            ("mean", rng.standard_normal(cout) * 0.1),
+            ("var", np.abs(rng.standard_normal(cout)) * 0.5 + 0.5))]
+        cur = gb.node("FusedBatchNormV3", f"{name}/bn", [c] + stats, T=f32,
+                      U=f32, epsilon=gb.a_float(1.001e-5),
+                      is_training=gb.a_bool(False),
+                      data_format=gb.a_str("NDHWC"))
+        if add_to is not None:
+            cur = gb.node("AddV2", f"{name}/add", [cur, add_to], T=f32)
+        if use_relu:
+            cur = gb.node("Relu", f"{name}/relu", [cur], T=f32)
+        return cur
+
+    def pool(op, name, x, k, stride, padding):
+        return gb.node(op, name, [x], T=f32, ksize=gb.a_ints([1, *k, 1]),
+                       strides=gb.a_ints([1, *stride, 1]),
+                       padding=gb.a_str(padding),
+                       data_format=gb.a_str("NDHWC"))
+
+    w1, w2 = width, width * 2
+    x = gb.placeholder("input", np.float32,
+                       [-1, frames, image_size, image_size, 3],
+                       signature_name="input")
+    h = conv("stem", x, 3, w1, (3, 7, 7), (1, 2, 2))
+    h = pool("MaxPool3D", "stem/pool", h, (1, 3, 3), (1, 2, 2), "SAME")
+    # R3D basic block
+    t = conv("r3d/c1", h, w1, w1, (3, 3, 3))
+    h = conv("r3d/c2", t, w1, w1, (3, 3, 3), add_to=h)
+    # R(2+1)D block: spatial then temporal
+    t = conv("r21d/spatial", h, w1, w1, (1, 3, 3))
+    h = conv("r21d/temporal", t, w1, w1, (3, 1, 1), add_to=h)
+    # strided stage, projection shortcut
+    sc = conv("down/shortcut", h, w1, w2, (1, 1, 1), (2, 2, 2),
+              use_relu=False)
+    t = conv("down/c1", h, w1, w2, (3, 3, 3), (2, 2, 2))
+    h = conv("down/c2", t, w2, w2, (3, 3, 3), add_to=sc)
+    h = conv("head", h, w2, w2 * 2, (1, 1, 1))
+    h = pool("AvgPool3D", "avgpool", h, (2, 2, 2), (2, 2, 2), "VALID")
+    pooled = gb.node("Mean", "gap",
+                     [h, gb.const("gap/axes",
+                                  np.array([1, 2, 3], dtype=np.int32))],
+                     T=f32, keep_dims=gb.a_bool(False))
+    cin = w2 * 2
+    wfc = gb.const("fc/w", (rng.standard_normal((cin, num_classes))
+                            * np.sqrt(1.0 / cin)).astype(np.float32))
+    bfc = gb.const("fc/b", np.zeros(num_classes, dtype=np.float32))
+    logits = gb.node("MatMul", "fc/mm", [pooled, wfc], T=f32)
+    logits = gb.node("BiasAdd", "logits", [logits, bfc], T=f32)
+    probs = gb.node("Softmax", "probs", [logits], T=f32)
+    gb.mark_output("probs", probs)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # repo writer
 # ---------------------------------------------------------------------------
 _BUILDERS = {
