@@ -167,7 +167,24 @@ static void launch_call(const Call& c, hipStream_t s) {
       // dilated one (groups written as 1)
       // The 23-int form [..15 as above.., groups, dh, dw (all 1),
       // D, T, sd, pf, Do] is a 3-D conv on [N,D,H,W,C]
+      // The 24-int form is the 23-int form plus a 24th int 1, "transposed":
+      // a 3-D transposed conv (Conv3DBackpropInputV2). N,D,H,W,C are x's
+      // extents, Do,Ho,Wo,Kc y's, T,R,S the full filter, pf,pt,pl the low
+      // pads of the forward conv; groups, dh, dw and the 24th int must be 1
       const ushort* res = c.ptrs[3] ? cp(3) : nullptr;
+      if (I.size() == 24) {
+        if (I[23] != 1 || I[15] != 1 || I[16] != 1 || I[17] != 1)
+          throw std::runtime_error(
+              "K_CONV 24-int form: groups, dh, dw and the transposed flag "
+              "must be 1");
+        launch_conv3d_transpose_igemm(
+            s, cp(0), cp(1), cp(2), res, cp(4), p(5), int(I[0]), int(I[18]),
+            int(I[1]), int(I[2]), int(I[3]), int(I[4]), int(I[19]),
+            int(I[5]), int(I[6]), int(I[20]), int(I[7]), int(I[8]),
+            int(I[21]), int(I[9]), int(I[10]), int(I[22]), int(I[11]),
+            int(I[12]), int(I[13]), int(I[14]));
+        break;
+      }
       if (I.size() == 23) {
         launch_conv3d_igemm(s, cp(0), cp(1), cp(2), res, cp(4), p(5),
                             int(I[0]), int(I[18]), int(I[1]), int(I[2]),

@@ -184,6 +184,29 @@ void launch_conv3d_igemm(hipStream_t s, const ushort* x, const ushort* w,
                          int T, int R, int S, int sd, int sh, int sw,
                          int pf, int pt, int pl, int Do, int Ho, int Wo,
                          int k_pad, int act, int groups, int dh, int dw);
+// 3-D transposed conv (K_CONV's 24-int form; Conv3DBackpropInputV2),
+// NDHWC: y[N,Do,Ho,Wo,Kc] = act(sum x[n,i,j,l,ci] * w[t,r,s,co,ci] + bias
+// [+ residual]) over od = i*sd - pf + t, oh = j*sh - pt + r,
+// ow = l*sw - pl + s, with (pf, pt, pl) the low pads of the forward conv
+// and x = [N,D,H,W,C]. One launch of a phase-split implicit GEMM: phase
+// (pd,ph,pw) = ((od+pf) % sd, ...) is a stride-1 conv over x with the taps
+// t = pd + sd*a, a < A(pd) = ceil((T - pd)/sd), so no inserted zero is
+// multiplied. w is [Kc][k_pad]: taps phase-major ((pd,ph,pw) row-major),
+// inside a phase ordered (a',b',c') with a' = A-1-a, channels innermost.
+// A phase's K range starts at a multiple of C and is walked in tiles of 64,
+// so when C % 64 != 0 its last tile runs past its last tap; the row holds
+// all-zero taps after the T*R*S real ones until the last tile of every
+// phase ends inside it, and k_pad = pad64(taps * C). Throws before any
+// launch on a k_pad that is not that, on C % 8 != 0, on any extent or
+// stride < 1, a negative pad, and on M or k beyond int32.
+void launch_conv3d_transpose_igemm(hipStream_t s, const ushort* x,
+                                   const ushort* w, const ushort* bias,
+                                   const ushort* residual,
+                                   const ushort* zeros, ushort* y,
+                                   int N, int D, int H, int W, int C, int Kc,
+                                   int T, int R, int S, int sd, int sh,
+                                   int sw, int pf, int pt, int pl, int Do,
+                                   int Ho, int Wo, int k_pad, int act);
 // dead-tap skipping of the dilated kernel: 0 never, 1 where it pays
 // (default: more than one block per CU and a filter reach of at least an
 // eighth of the image), 2 wherever C % 64 == 0. A measurement switch

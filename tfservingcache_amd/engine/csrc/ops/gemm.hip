@@ -21,6 +21,7 @@
 #include "../common.h"
 #include "../kernels.h"
 
+#include <algorithm>
 #include <stdexcept>
 
 namespace tfsc {
@@ -1333,6 +1334,377 @@ void launch_conv3d_igemm(hipStream_t s, const ushort* x, const ushort* w,
   else if (residual)   launch(conv3d_igemm_kernel<true, false>);
   else if (uni)        launch(conv3d_igemm_kernel<false, true>);
   else                 launch(conv3d_igemm_kernel<false, false>);
+}
+
+// ---------------------------------------------------------------------------
+// 3-D transposed conv (Conv3DBackpropInputV2; 3-D U-Net / V-Net decoders),
+// phase-split ("sub-pixel") implicit GEMM, one launch:
+//   y[n,od,oh,ow,co] = sum x[n,i,j,l,ci] * w[t,r,s,co,ci],  od = i*sd - pf + t
+// Per axis an output coordinate od has phase pd = (od + pf) mod sd and only
+// meets taps t = pd + sd*a, a in [0, A(pd)), A(pd) = ceil((T - pd)/sd) (0
+// when pd >= T), at input i = q - a with q = (od + pf) div sd. So each of
+// the sd*sh*sw phases is a stride-1 conv over the un-dilated x with an
+// A x B x Cc sub-filter that writes one strided sub-lattice of y; no tap
+// multiplies an inserted zero.
+//  - grid: phases x M tiles x N tiles. A block decodes (pd, ph, pw) from
+//    its id and derives, per axis, A, the phase's first q (q0), its count
+//    of q (Q) and the taps of the phases before it, all block-uniform
+//    (phase_axis below; no device-side table). M_phase = N*Qd*Qh*Qw; Q
+//    differs by at most 1 between phases, the M-tile count is sized by the
+//    largest and a block with m0 >= M_phase returns before any barrier.
+//  - weights: [Kc][k_pad], taps phase-major ((pd,ph,pw) row-major), inside
+//    a phase in (a',b',c') order with a' = A-1-a (reversed), k = (taps
+//    before + (a'*B + b')*Cc + c')*C + ci. Reversed taps make the cursor
+//    walk forward through x from the corner (qd-(A-1), qh-(B-1),
+//    qw-(Cc-1)): conv3d_igemm_kernel's org + koff gather with (T,R,S)
+//    replaced by (A,B,Cc), TAP_UNIFORM included.
+//  - a phase's k range starts at a multiple of C, not of 64: with
+//    C % 64 != 0 its last K tile runs past its last tap. A reads the zero
+//    page there (a' >= A), so whatever finite weights B holds there do not
+//    count, but the tile must lie inside the row: the row carries all-zero
+//    taps after the real ones until it does (conv3d_transpose_taps).
+//  - a phase with no tap (filter smaller than the stride) has zero K
+//    tiles: nothing is staged and the epilogue writes act(bias [+ res]).
+//  - epilogue: epilogue_store_f32's staging with the global row offset
+//    replaced by the voxel's, (((n*Do + od)*Ho + oh)*Wo + ow)*Kc, for the
+//    store and the residual read alike.
+// ---------------------------------------------------------------------------
+struct Conv3dTGeom {
+  int N, D, H, W, C, T, R, S, sd, sh, sw, pf, pt, pl, Do, Ho, Wo, ntm, ntn;
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                   \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+// one axis of a phase: taps A, first q, count of q, taps of earlier phases
+struct PhaseAxis {
+  int A, q0, Q, pref;
+};
+
+__host__ __device__ inline PhaseAxis phase_axis(int p, int T, int s, int pad,
+                                                int out) {
+  PhaseAxis a;
+  a.A = p < T ? (T - p + s - 1) / s : 0;
+  a.q0 = p >= pad ? 0 : (pad - p + s - 1) / s;
+  int last = out - 1 + pad - p;           // largest od + pad - p
+  a.Q = last < 0 ? 0 : last / s - a.q0 + 1;
+  a.Q = a.Q < 0 ? 0 : a.Q;
+  a.pref = (T / s) * p + (T % s < p ? T % s : p);   // |{t < T: t mod s < p}|
+  return a;
+}
+
+// epilogue_store_f32 with the output row scattered: row_off(grow) is the
+// element offset of row grow's Kc contiguous channels in y and residual
+template <bool HAS_RES, class RowOff>
+TFSC_DEV void epilogue_scatter_f32(f32x4_t (&acc)[4][4], char* smem,
+                                   const ushort* __restrict__ bias,
+                                   const ushort* __restrict__ residual,
+                                   ushort* __restrict__ Cb, RowOff row_off,
+                                   int M, int N, int m0, int n0, int wave,
+                                   int lane, int wm, int wn, int act) {
+  __syncthreads();              // tiles are dead; reuse as staging
+  float* stage = reinterpret_cast<float*>(smem + wave * 16384);
+  const int col_in = lane & 15;
+  const int row_base = (lane >> 4) * 4;
+  #pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+    #pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      int col = ni * 16 + col_in;
+      float bv = bf2f(bias[n0 + wn * 64 + col]);
+      #pragma unroll
+      for (int r = 0; r < 4; ++r)
+        stage[(mi * 16 + row_base + r) * 64 + col] = acc[mi][ni][r] + bv;
+    }
+  }
+  __syncthreads();
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    int chunk_id = i * 64 + lane;
+    int row = chunk_id >> 3;
+    int chunk = chunk_id & 7;
+    int grow = m0 + wm * 64 + row;
+    int gcol0 = n0 + wn * 64 + chunk * 8;
+    if (grow >= M || gcol0 >= N) continue;
+    const f32x4_t* sp =
+        reinterpret_cast<const f32x4_t*>(stage + row * 64 + chunk * 8);
+    f32x4_t lo = sp[0], hi = sp[1];
+    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    int64_t goff = row_off(grow) + gcol0;
+    const bool full = gcol0 + 7 < N;
+    if (HAS_RES) {
+      if (full) {
+        bf16x8 rv = *reinterpret_cast<const bf16x8*>(residual + goff);
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += bf2f((ushort)rv[j]);
+      } else {
+        for (int j = 0; j < 8 && gcol0 + j < N; ++j)
+          v[j] += bf2f(residual[goff + j]);
+      }
+    }
+    bf16x8 o;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (short)f2bf(act_apply(v[j], act));
+    if (full) {
+      *reinterpret_cast<bf16x8*>(Cb + goff) = o;
+    } else {
+      for (int j = 0; j < 8 && gcol0 + j < N; ++j)
+        Cb[goff + j] = (ushort)o[j];
+    }
+  }
+}
+
+template <bool HAS_RES, bool TAP_UNIFORM>
+__global__ __launch_bounds__(THREADS)
+void conv3d_transpose_igemm_kernel(const ushort* __restrict__ x,
+                                   const ushort* __restrict__ B,
+                                   const ushort* __restrict__ bias,
+                                   const ushort* __restrict__ residual,
+                                   const ushort* __restrict__ zeros,
+                                   ushort* __restrict__ Cout,
+                                   int N, int K, int act, Conv3dTGeom g) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * BM * BK * 2];
+  auto lds_a = [&](int buf) -> char* { return smem + buf * 32768; };
+  auto lds_b = [&](int buf) -> char* { return smem + 16384 + buf * 32768; };
+
+  // block -> (phase, N tile, M tile), M fastest; all of it block-uniform
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int tile_m = bid % g.ntm;
+  int rest = bid / g.ntm;
+  const int tile_n = rest % g.ntn;
+  rest /= g.ntn;
+  const int pw = rest % g.sw;
+  rest /= g.sw;
+  const int ph = rest % g.sh;
+  const int pd = rest / g.sh;
+  const PhaseAxis ad = phase_axis(pd, g.T, g.sd, g.pf, g.Do);
+  const PhaseAxis ah = phase_axis(ph, g.R, g.sh, g.pt, g.Ho);
+  const PhaseAxis aw = phase_axis(pw, g.S, g.sw, g.pl, g.Wo);
+  const int M = g.N * ad.Q * ah.Q * aw.Q;     // the launcher bounds it
+  const int m0 = tile_m * BM;
+  if (m0 >= M) return;                        // before the first barrier
+  const int n0 = tile_n * BN;
+  const int n_taps = ad.A * ah.A * aw.A;
+  const int n_ktiles = (n_taps * g.C + BK - 1) / BK;
+  const int k_base =
+      (ad.pref * g.R * g.S + ad.A * (ah.pref * g.S + ah.A * aw.pref)) * g.C;
+
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int r_in = lane >> 3;
+  const int chunk_src = (lane & 7) ^ r_in;    // row & 7 == r_in
+
+  // the lane's four A rows: m -> (n, qd, qh, qw), the corner
+  // (qd-(A-1), qh-(B-1), qw-(Cc-1)) of the sub-filter's reach and its
+  // offset in x (negative in the padding; only added to in-volume taps)
+  int di0[4], hi0[4], wi0[4];
+  int64_t org[4];
+  if (n_ktiles > 0) {
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int m = m0 + wave * 32 + i * 8 + r_in;
+      m = m < M - 1 ? m : M - 1;
+      int jw = m % aw.Q;
+      int q = m / aw.Q;
+      int jh = q % ah.Q;
+      q /= ah.Q;
+      int n = q / ad.Q;
+      di0[i] = ad.q0 + q % ad.Q - (ad.A - 1);
+      hi0[i] = ah.q0 + jh - (ah.A - 1);
+      wi0[i] = aw.q0 + jw - (aw.A - 1);
+      org[i] = ((((int64_t)n * g.D + di0[i]) * g.H + hi0[i]) * g.W + wi0[i]) *
+               g.C;
+    }
+  }
+
+  // the k cursor inside the phase: reversed tap (kt, kr, ks) = (a', b', c')
+  // and channel kc of the lane's chunk (TAP_UNIFORM: of the tile's first
+  // chunk); koff = ((kt*H + kr)*W + ks)*C + kc, the chunk's offset from a
+  // row's corner
+  int kt = 0, kr = 0, ks = 0, kc = 0;
+  if (!TAP_UNIFORM && n_ktiles > 0) {
+    int k = chunk_src * 8;
+    kc = k % g.C;
+    int q = k / g.C;
+    ks = q % aw.A;
+    q /= aw.A;
+    kr = q % ah.A;
+    kt = q / ah.A;
+  }
+  int64_t koff = (((int64_t)kt * g.H + kr) * g.W + ks) * g.C + kc;
+  const int64_t r_jump = (int64_t)(g.W - aw.A) * g.C;
+  const int64_t t_jump = (int64_t)(g.H - ah.A) * g.W * g.C;
+
+  // stage the K tile the cursor stands on (k0 is its first k in the
+  // phase), then step
+  auto stage = [&](int k0, int buf) {
+    const int64_t off = TAP_UNIFORM ? koff + chunk_src * 8 : koff;
+    const bool k_ok = TAP_UNIFORM || kt < ad.A;
+    char* lds_tile = lds_a(buf);
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned di = unsigned(di0[q] + kt);    // negative wraps above D
+      unsigned hi = unsigned(hi0[q] + kr);
+      unsigned wi = unsigned(wi0[q] + ks);
+      bool ok = k_ok & (di < unsigned(g.D)) & (hi < unsigned(g.H)) &
+                (wi < unsigned(g.W));
+      const ushort* gptr = ok ? x + (org[q] + off) : zeros;
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const uint32_t*>(gptr),
+          reinterpret_cast<uint32_t*>(lds_tile + (wave * 32 + q * 8) * 128),
+          16, 0, 0);
+    }
+    stage_tile_glds<128, 4>(B, K, N - 1, n0, k_base + k0, lds_b(buf), wave,
+                            lane);
+    kc += BK;
+    koff += BK;
+    while (kc >= g.C) {                       // C >= 64: at most once
+      kc -= g.C;
+      if (++ks == aw.A) {
+        ks = 0;
+        koff += r_jump;
+        if (++kr == ah.A) {
+          kr = 0;
+          koff += t_jump;
+          ++kt;
+        }
+      }
+    }
+  };
+
+  f32x4_t acc[4][4] = {};
+
+  if (n_ktiles > 0) stage(0, 0);
+
+  int cur = 0;
+  for (int i = 0; i < n_ktiles; ++i) {
+    __syncthreads();
+    if (i + 1 < n_ktiles) stage((i + 1) * BK, cur ^ 1);
+    const char* at = lds_a(cur);
+    const char* bt = lds_b(cur);
+    const int frow = lane & 15;
+    const int kgrp = lane >> 4;
+    #pragma unroll
+    for (int kstep = 0; kstep < 2; ++kstep) {
+      bf16x8_t a_frag[4], b_frag[4];
+      const int chunk = kstep * 4 + kgrp;
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        a_frag[mi] = *reinterpret_cast<const bf16x8_t*>(
+            at + lds_off(wm * 64 + mi * 16 + frow, chunk));
+      #pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+        b_frag[ni] = *reinterpret_cast<const bf16x8_t*>(
+            bt + lds_off(wn * 64 + ni * 16 + frow, chunk));
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_frag[mi], b_frag[ni], acc[mi][ni], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    cur ^= 1;
+  }
+
+  // row of the phase -> its voxel of y: od = qd*sd + pd - pf, likewise h, w
+  auto row_off = [&](int m) -> int64_t {
+    int jw = m % aw.Q;
+    int q = m / aw.Q;
+    int jh = q % ah.Q;
+    q /= ah.Q;
+    int n = q / ad.Q;
+    int od = (ad.q0 + q % ad.Q) * g.sd + pd - g.pf;
+    int oh = (ah.q0 + jh) * g.sh + ph - g.pt;
+    int ow = (aw.q0 + jw) * g.sw + pw - g.pl;
+    return ((((int64_t)n * g.Do + od) * g.Ho + oh) * g.Wo + ow) * N;
+  };
+  epilogue_scatter_f32<HAS_RES>(acc, smem, bias, residual, Cout, row_off, M,
+                                N, m0, n0, wave, lane, wm, wn, act);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+// taps of the weight row: T*R*S real ones, then zero taps until the last K
+// tile of every non-empty phase ends inside the row
+static int64_t conv3d_transpose_taps(int C, int T, int R, int S, int sd,
+                                     int sh, int sw) {
+  int64_t need = 0;
+  for (int pd = 0; pd < sd && pd < T; ++pd)
+    for (int ph = 0; ph < sh && ph < R; ++ph)
+      for (int pw = 0; pw < sw && pw < S; ++pw) {
+        PhaseAxis a = phase_axis(pd, T, sd, 0, 1);   // A and pref only
+        PhaseAxis b = phase_axis(ph, R, sh, 0, 1);
+        PhaseAxis c = phase_axis(pw, S, sw, 0, 1);
+        int64_t before = (int64_t)a.pref * R * S +
+                         (int64_t)a.A * (b.pref * S + b.A * c.pref);
+        int64_t kp = (int64_t)a.A * b.A * c.A * C;
+        int64_t end = before * C + (kp + BK - 1) / BK * BK;
+        need = end > need ? end : need;
+      }
+  return (need + C - 1) / C;
+}
+
+void launch_conv3d_transpose_igemm(hipStream_t s, const ushort* x,
+                                   const ushort* w, const ushort* bias,
+                                   const ushort* residual,
+                                   const ushort* zeros, ushort* y,
+                                   int N_img, int D, int H, int W, int C,
+                                   int Kc, int T, int R, int S, int sd,
+                                   int sh, int sw, int pf, int pt, int pl,
+                                   int Do, int Ho, int Wo, int k_pad,
+                                   int act) {
+  if (N_img < 1 || D < 1 || H < 1 || W < 1 || C < 1 || Kc < 1 || T < 1 ||
+      R < 1 || S < 1 || sd < 1 || sh < 1 || sw < 1 || Do < 1 || Ho < 1 ||
+      Wo < 1)
+    throw std::runtime_error(
+        "conv3d_transpose_igemm: every extent and stride must be >= 1");
+  if (pf < 0 || pt < 0 || pl < 0)
+    throw std::runtime_error("conv3d_transpose_igemm: negative pad");
+  if (C % 8 != 0)
+    throw std::runtime_error("conv3d_transpose_igemm requires C % 8 == 0");
+  if ((int64_t)T * R * S * C > INT32_MAX / 4)
+    throw std::runtime_error("conv3d_transpose_igemm: T*R*S*C beyond int32");
+  // the weight row: see conv3d_transpose_taps
+  int64_t row = conv3d_transpose_taps(C, T, R, S, sd, sh, sw) * C;
+  if (k_pad != (row + BK - 1) / BK * BK)
+    throw std::runtime_error(
+        "conv3d_transpose_igemm k_pad must be pad64(taps * C), taps being "
+        "T*R*S plus the zero taps that keep every phase's last K tile in "
+        "the row");
+  // the largest phase: the per-axis maxima of Q
+  int64_t qmax[3] = {0, 0, 0};
+  for (int p = 0; p < sd; ++p)
+    qmax[0] = std::max<int64_t>(qmax[0], phase_axis(p, T, sd, pf, Do).Q);
+  for (int p = 0; p < sh; ++p)
+    qmax[1] = std::max<int64_t>(qmax[1], phase_axis(p, R, sh, pt, Ho).Q);
+  for (int p = 0; p < sw; ++p)
+    qmax[2] = std::max<int64_t>(qmax[2], phase_axis(p, S, sw, pl, Wo).Q);
+  int64_t M = N_img * qmax[0] * qmax[1] * qmax[2];
+  if (M > INT32_MAX - BM || (int64_t)N_img * Do * Ho * Wo > INT32_MAX - BM)
+    throw std::runtime_error(
+        "conv3d_transpose_igemm: more than 2^31 output voxels");
+  int ntm = int(ceil_div(M, BM)), ntn = int(ceil_div(Kc, BN));
+  int64_t blocks = (int64_t)sd * sh * sw * ntm * ntn;
+  if (blocks > INT32_MAX)
+    throw std::runtime_error("conv3d_transpose_igemm: grid beyond int32");
+  Conv3dTGeom g{N_img, D, H, W, C, T, R, S, sd, sh, sw, pf, pt, pl,
+                Do, Ho, Wo, ntm, ntn};
+  dim3 grid((unsigned)blocks);
+  bool uni = C % BK == 0;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, x, w, bias, residual,
+                       zeros, y, Kc, k_pad, act, g);
+  };
+  if (residual && uni) launch(conv3d_transpose_igemm_kernel<true, true>);
+  else if (residual)   launch(conv3d_transpose_igemm_kernel<true, false>);
+  else if (uni)        launch(conv3d_transpose_igemm_kernel<false, true>);
+  else                 launch(conv3d_transpose_igemm_kernel<false, false>);
 }
 
 void launch_batched_gemm(hipStream_t s, const ushort* A, const ushort* B,

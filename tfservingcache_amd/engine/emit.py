@@ -28,7 +28,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .planner import Plan, PlanOp
+from .planner import Plan, PlanOp, conv3d_transpose_taps
 
 ALIGN = 256  # byte alignment of workspace slices
 
@@ -282,7 +282,7 @@ class _Emitter:
                     H, W = op.params["hw"]
                     c8 = (Cin + 7) // 8 * 8
                     scratch_sizes[oi] = self.batch * H * W * c8 * 2
-            if op.kind == "conv3d":
+            if op.kind in ("conv3d", "conv3d_transpose"):
                 # the same channel-pad scratch, over N*D*H*W rows
                 Cin = op.params["trsck"][3]
                 if Cin % 8 != 0:
@@ -416,6 +416,8 @@ class _Emitter:
                 self._c_conv(op, oi)
             elif k == "conv3d":
                 self._c_conv3d(op, oi)
+            elif k == "conv3d_transpose":
+                self._c_conv3d_transpose(op, oi)
             elif k == "batched_gemm":
                 self._c_bgemm(op)
             elif k == "attention":
@@ -777,6 +779,44 @@ class _Emitter:
             self._call("CONV",
                        [scratch, (("cw", w_idx, "cpad", c8), 0), bias, res,
                         zeros, out], ints(c8))
+
+    def _c_conv3d_transpose(self, op: PlanOp, oi: int) -> None:
+        """CONV's 24-int form: the 23-int form's slots with x's extents in
+        N,D,H,W,C, y's in Do,Ho,Wo,Kc, the full filter in T,R,S, the low
+        pads of the forward conv in pf,pt,pl, and a 24th int 1,
+        "transposed". The master weight is [n_taps,1,Ci,Co] in the kernel's
+        phase-major tap order (planner.conv3d_transpose_phases), so
+        ("cw", idx) is [Kc][pad64(n_taps*C)]; C % 8 != 0 is widened as in
+        _c_conv3d."""
+        p = op.params
+        T, R, S, C, Kc = p["trsck"]
+        sd, sh, sw = p["stride"]
+        pf, pt, pl = p["pads"]
+        Do, Ho, Wo = p["out_dhw"]
+        x, w_idx = op.inputs[0], op.inputs[1]
+        n, D, H, W, xC = self.shapes[x]
+        c8 = (C + 7) // 8 * 8
+        n_taps = conv3d_transpose_taps((T, R, S), (sd, sh, sw), c8)
+        if self._weight_shape(w_idx) != (n_taps, 1, C, Kc) or xC != C:
+            raise KeyError(f"no [n_taps,1,Ci,Co] master weight for tensor "
+                           f"{w_idx}")
+        bias = self._weight(op.inputs[2])
+        res = self._ptr(op.inputs[3]) if p.get("residual") else None
+        out = self._ptr(op.outputs[0])
+        zeros = (("zeros",), 0)
+        ints = [n, H, W, c8, Kc, R, S, sh, sw, pt, pl, Ho, Wo,
+                _pad64(n_taps * c8), _act(p), 1, 1, 1, D, T, sd, pf, Do, 1]
+        if C % 8 == 0:
+            self._call("CONV",
+                       [self._ptr(x), (("cw", w_idx), 0), bias, res, zeros,
+                        out], ints)
+        else:
+            scratch = self._scratch(oi)
+            self._call("PAD_LAST", [self._ptr(x), scratch],
+                       [n * D * H * W, C, c8])
+            self._call("CONV",
+                       [scratch, (("cw", w_idx, "cpad", c8), 0), bias, res,
+                        zeros, out], ints)
 
     def _c_bgemm(self, op: PlanOp) -> None:
         p = op.params

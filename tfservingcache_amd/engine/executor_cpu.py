@@ -13,7 +13,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .planner import Plan, PlanOp
+from .planner import Plan, PlanOp, conv3d_transpose_phases
 
 
 def _act(x: np.ndarray, act: str) -> np.ndarray:
@@ -190,6 +190,8 @@ class CpuExecutor:
             self._conv3d(op, _get, vals)
         elif k == "pool3d":
             self._pool3d(op, _get, vals)
+        elif k == "conv3d_transpose":
+            self._conv3d_transpose(op, _get, vals)
         elif k == "global_mean":
             x = _get(op.inputs[0])
             y = x.mean(axis=(1, 2), keepdims=p.get("keep", False))
@@ -408,6 +410,30 @@ class CpuExecutor:
             cols[..., i * C:(i + 1) * C] = patch
         y = cols.reshape(-1, T * R * S * C) @ w.reshape(-1, K)
         y = y.reshape(x.shape[0], Do, Ho, Wo, K) + b
+        if p.get("residual"):
+            y = y + _get(op.inputs[3])
+        vals[op.outputs[0]] = _act(y, p.get("act", "none")).astype(np.float32)
+
+    def _conv3d_transpose(self, op: PlanOp, _get, vals) -> None:
+        x = _get(op.inputs[0])          # [N,D,H,W,Ci]
+        w = _get(op.inputs[1])          # [n_taps,1,Ci,Co], phase-major taps
+        b = _get(op.inputs[2])          # [Co]
+        p = op.params
+        T, R, S, Ci, Co = p["trsck"]
+        sd, sh, sw = p["stride"]
+        N, D, H, W, _ = x.shape
+        # the uncropped result: tap (t,r,s) of x[i,j,l] lands on
+        # (i*sd + t, j*sh + r, l*sw + s); at least pad + out long per axis
+        full = [max((n - 1) * st + k, lo + o) for n, st, k, lo, o in zip(
+            (D, H, W), p["stride"], (T, R, S), p["pads"], p["out_dhw"])]
+        yf = np.zeros((N, *full, Co), dtype=np.float32)
+        for _phase, taps, first in conv3d_transpose_phases((T, R, S),
+                                                           p["stride"]):
+            for i, (t, r, s) in enumerate(taps):
+                yf[:, t:t + (D - 1) * sd + 1:sd, r:r + (H - 1) * sh + 1:sh,
+                   s:s + (W - 1) * sw + 1:sw, :] += x @ w[first + i, 0]
+        (pf, pt, pl), (Do, Ho, Wo) = p["pads"], p["out_dhw"]
+        y = yf[:, pf:pf + Do, pt:pt + Ho, pl:pl + Wo, :] + b
         if p.get("residual"):
             y = y + _get(op.inputs[3])
         vals[op.outputs[0]] = _act(y, p.get("act", "none")).astype(np.float32)

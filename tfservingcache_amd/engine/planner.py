@@ -399,6 +399,9 @@ class _Lowerer:
         if op in ("MaxPool3D", "AvgPool3D"):
             self.lower_pool3d(nd, out)
             return
+        if op == "Conv3DBackpropInputV2" and len(nd.input) == 3:
+            self.lower_conv3d_backprop_input(nd, out)
+            return
         if op == "Einsum":
             self.lower_einsum(nd, out)
             return
@@ -928,6 +931,103 @@ class _Lowerer:
         self.ops.append(PlanOp("conv3d", inputs, [y], params))
         if out_name != out:
             self.by_name[out] = y   # conv node's own tensor name -> fused out
+
+    def lower_conv3d_backprop_input(self, nd: g.NodeDef, out: str) -> None:
+        """Conv3DBackpropInputV2 (Keras Conv3DTranspose), NDHWC, dilation 1:
+            y[n, i*sd-pf+t, j*sh-pt+r, l*sw-pl+s, co] += x[n,i,j,l,ci] *
+                                                         w[t,r,s,co,ci]
+        with (pf, pt, pl) the low pads of the forward conv it is the
+        gradient of -> one conv3d_transpose op on the phase-split kernel
+        (no zero insertion). BiasAdd / BN / residual / activation fold in.
+        The filter is rewritten here into the kernel's tap order (see
+        conv3d_transpose_phases) as the rank-4 master [n_taps,1,Ci,Co], so
+        the conv weight transforms give [Co][pad64(n_taps*C)] unchanged;
+        n_taps includes the zero taps of conv3d_transpose_taps, counted for
+        the channel count the kernel sees (Ci widened to a multiple of 8).
+        The op carries trsck (T,R,S,Ci,Co), stride, pads (pf,pt,pl), dhw,
+        out_dhw and act."""
+        who = f"Conv3DBackpropInputV2 {nd.name}"
+        if _attr_s(nd, "data_format", "NDHWC") != "NDHWC":
+            raise PlanError(f"{who}: only NDHWC supported (data_format "
+                            f"{_attr_s(nd, 'data_format')})")
+        dil = _attr_ints(nd, "dilations") or [1] * 5
+        if any(d != 1 for d in dil):
+            raise PlanError(f"dilated {who} unsupported ({dil})")
+        padding = _attr_s(nd, "padding", "VALID")
+        if padding not in ("SAME", "VALID"):
+            raise PlanError(f"{who}: padding {padding}")
+        sizes = self.const_value(nd.input[0])
+        if sizes is None or np.size(sizes) != 5:
+            raise PlanError(f"{who}: input_sizes {nd.input[0]} must be a "
+                            f"constant [N,D,H,W,C]")
+        sizes = [int(v) for v in np.asarray(sizes).reshape(-1)]
+        w_v = self.const_value(nd.input[1])
+        if w_v is None or np.ndim(w_v) != 5:
+            raise PlanError(f"{who}: the filter {nd.input[1]} must be a "
+                            f"constant [T,R,S,Co,Ci]")
+        w = np.asarray(w_v, dtype=np.float32)
+        T, R, S, Co, Ci = w.shape
+        x = self.tid(nd.input[2])
+        xt = self.tensors[x]
+        xs = xt.shape
+        if len(xs) != 5 or xt.dtype != "f32" or \
+                any(is_sym(d) for d in xs[1:]):
+            raise PlanError(f"{who}: needs an f32 [B,D,H,W,Ci] input with "
+                            f"concrete D, H, W and Ci (got {xs})")
+        if int(xs[4]) != Ci or sizes[4] != Co:
+            raise PlanError(f"{who}: channels: filter {w.shape}, x {xs}, "
+                            f"input_sizes {sizes}")
+        st = _attr_ints(nd, "strides") or [1] * 5
+        if len(st) != 5 or st[0] != 1 or st[4] != 1 or min(st) < 1:
+            raise PlanError(f"{who}: batch or channel stride unsupported "
+                            f"(strides {st})")
+        stride, dhw, out_dhw = tuple(st[1:4]), tuple(int(d) for d in xs[1:4]), \
+            tuple(sizes[1:4])
+        pads = []
+        for size, o, k, s in zip(dhw, out_dhw, (T, R, S), stride):
+            # the forward conv on an extent of o must produce size
+            expect = -(-o // s) if padding == "SAME" else (o - k) // s + 1
+            if o < 1 or expect != size:
+                raise PlanError(
+                    f"{who}: input_sizes {sizes} is inconsistent with x "
+                    f"{dhw} ({padding}, strides {stride}, filter "
+                    f"{(T, R, S)})")
+            tot = max((size - 1) * s + k - o, 0) if padding == "SAME" else 0
+            pads.append(tot // 2)
+
+        bias, bn, residual, act, final = self._absorb_act_chain(nd)
+        if bn is not None:
+            scale, offset, mean, var, eps = bn
+            g_ = scale / np.sqrt(var + eps)
+            w = w * g_.reshape(1, 1, 1, Co, 1)
+            base = bias if bias is not None else np.zeros(Co, np.float32)
+            bias = (base - mean) * g_ + offset
+        if bias is None:
+            bias = np.zeros(Co, np.float32)
+        c8 = (Ci + 7) // 8 * 8
+        wm = np.zeros((conv3d_transpose_taps((T, R, S), stride, c8), 1, Ci,
+                       Co), np.float32)
+        for _phase, taps, first in conv3d_transpose_phases((T, R, S),
+                                                           stride):
+            for i, (t, r, s) in enumerate(taps):
+                wm[first + i, 0] = w[t, r, s].T         # [Co,Ci] -> [Ci,Co]
+        w_id = self.new_tensor(tuple(wm.shape), "f32", "weight",
+                               f"{nd.name}/fused_w", weight=wm)
+        b_id = self.new_tensor((Co,), "f32", "weight",
+                               f"{nd.name}/fused_b", weight=bias)
+        out_name = f"{final.name}:0"
+        y = self.new_tensor((xs[0],) + out_dhw + (Co,), "f32", "activation",
+                            out_name)
+        inputs = [x, w_id, b_id]
+        params = {"trsck": (T, R, S, Ci, Co), "stride": stride,
+                  "pads": tuple(pads), "dhw": dhw, "out_dhw": out_dhw,
+                  "act": act}
+        if residual is not None:
+            inputs.append(self.tid(residual))
+            params["residual"] = True
+        self.ops.append(PlanOp("conv3d_transpose", inputs, [y], params))
+        if out_name != out:
+            self.by_name[out] = y
 
     def lower_pool3d(self, nd: g.NodeDef, out: str) -> None:
         """MaxPool3D / AvgPool3D (NDHWC) -> one pool3d op. The average
@@ -1983,6 +2083,37 @@ def _merge_groups(w: np.ndarray, G: int, m_: int) -> np.ndarray:
         out[:, :, i * Cg:(i + 1) * Cg, g_ * Ng:(g_ + 1) * Ng] = \
             w[:, :, :, g_ * Ng:(g_ + 1) * Ng]
     return out
+
+
+def conv3d_transpose_phases(trs, stride):
+    """The tap order of a conv3d_transpose weight. A transposed conv of
+    stride (sd,sh,sw) splits into sd*sh*sw phases: an output coordinate od
+    with (od + pf) % sd == pd only meets taps t = pd + sd*a. Yields, for
+    the phases in row-major (pd,ph,pw) order, ((pd,ph,pw), taps, first):
+    the phase's filter taps (t,r,s) in stored order - each axis reversed,
+    a' = A-1-a, so that walking them walks forward through x - and the
+    index of its first tap in the weight. A phase with no tap (filter
+    smaller than the stride) yields an empty list."""
+    per_axis = [[list(range(p, k, s))[::-1] for p in range(s)]
+                for k, s in zip(trs, stride)]
+    first = 0
+    for pd, ts in enumerate(per_axis[0]):
+        for ph, rs in enumerate(per_axis[1]):
+            for pw, ss in enumerate(per_axis[2]):
+                taps = [(t, r, s) for t in ts for r in rs for s in ss]
+                yield (pd, ph, pw), taps, first
+                first += len(taps)
+
+
+def conv3d_transpose_taps(trs, stride, c: int) -> int:
+    """Taps in a conv3d_transpose weight row for c (a multiple of 8)
+    channels per tap: the T*R*S real ones, then all-zero taps until the
+    last 64-wide K tile of every phase, counted from the phase's first k,
+    ends inside the row. Only c % 64 != 0 adds any."""
+    need = max(first * c + -(-len(taps) * c // 64) * 64
+               for _p, taps, first in conv3d_transpose_phases(trs, stride)
+               if taps)
+    return -(-need // c)
 
 
 def _broadcast(sa: Sequence[Dim], sb: Sequence[Dim]) -> Shape:

@@ -1060,6 +1060,109 @@ def build_video_resnet(frames=8, image_size=32, num_classes=10, seed=0,
 
 
 # ---------------------------------------------------------------------------
+# 3-D U-Net (NDHWC, inference): the volumetric segmentation family (3-D
+# U-Net, V-Net) in one small graph. Conv3D + BN + relu encoder with
+# MaxPool3D, a decoder that upsamples by Conv3DBackpropInputV2 (Keras
+# Conv3DTranspose: input_sizes is Pack([batch, D, H, W, C])) - a 2x2x2/2
+# step with BN + relu and a 3x3x3/2 SAME step with BiasAdd + relu - skip
+# connections by ConcatV2, a 1x1x1 head and a softmax over the classes.
+# ---------------------------------------------------------------------------
+def build_unet3d(depth=8, image_size=16, in_ch=3, base=16, num_classes=4,
+                 seed=0):
+    """depth and image_size must be multiples of 4."""
+    if depth % 4 or image_size % 4:
+        raise ValueError("build_unet3d: depth and image_size must be "
+                         "multiples of 4")
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32, i32 = gb.a_type(1), gb.a_type(3)
+
+    def weight(name, shape, fan_in):
+        return gb.const(name, (rng.standard_normal(shape)
+                               * np.sqrt(2.0 / fan_in)).astype(np.float32))
+
+    def bn_relu(name, x, ch):
+        stats = [gb.const(f"{name}/{n}", v.astype(np.float32)) for n, v in (
+            ("gamma", np.abs(rng.standard_normal(ch)) * 0.5 + 0.5),
+            ("beta", rng.standard_normal(ch) * 0.1),
+            ("mean", rng.standard_normal(ch) * 0.1),
+            ("var", np.abs(rng.standard_normal(ch)) * 0.5 + 0.5))]
+        y = gb.node("FusedBatchNormV3", f"{name}/bn", [x] + stats, T=f32,
+                    U=f32, epsilon=gb.a_float(1.001e-5),
+                    is_training=gb.a_bool(False),
+                    data_format=gb.a_str("NDHWC"))
+        return gb.node("Relu", f"{name}/relu", [y], T=f32)
+
+    def conv(name, x, cin, cout):
+        c = gb.node("Conv3D", f"{name}/conv",
+                    [x, weight(f"{name}/w", (3, 3, 3, cin, cout), 27 * cin)],
+                    T=f32, strides=gb.a_ints([1] * 5),
+                    padding=gb.a_str("SAME"), data_format=gb.a_str("NDHWC"))
+        return bn_relu(name, c, cout)
+
+    def pool(name, x):
+        return gb.node("MaxPool3D", name, [x], T=f32,
+                       ksize=gb.a_ints([1, 2, 2, 2, 1]),
+                       strides=gb.a_ints([1, 2, 2, 2, 1]),
+                       padding=gb.a_str("VALID"),
+                       data_format=gb.a_str("NDHWC"))
+
+    def deconv(name, x, cin, cout, k, out_dhw, padding):
+        shp = gb.node("Shape", f"{name}/shape", [x], T=f32, out_type=i32)
+        batch = gb.node(
+            "StridedSlice", f"{name}/batch",
+            [shp, gb.const(f"{name}/ss_b", np.array([0], np.int32)),
+             gb.const(f"{name}/ss_e", np.array([1], np.int32)),
+             gb.const(f"{name}/ss_s", np.array([1], np.int32))],
+            T=i32, Index=i32, shrink_axis_mask=gb.a_int(1))
+        sizes = gb.node(
+            "Pack", f"{name}/input_sizes",
+            [batch] + [gb.const(f"{name}/o{i}", np.int32(v))
+                       for i, v in enumerate((*out_dhw, cout))],
+            T=i32, N=gb.a_int(5), axis=gb.a_int(0))
+        return gb.node("Conv3DBackpropInputV2", f"{name}/deconv",
+                       [sizes, weight(f"{name}/w", (k, k, k, cout, cin),
+                                      k ** 3 * cin), x],
+                       T=f32, strides=gb.a_ints([1, 2, 2, 2, 1]),
+                       padding=gb.a_str(padding),
+                       data_format=gb.a_str("NDHWC"))
+
+    def concat(name, a, b):
+        return gb.node("ConcatV2", name,
+                       [a, b, gb.const(f"{name}/axis", np.int32(4))], T=f32,
+                       N=gb.a_int(2), Tidx=i32)
+
+    d, s = depth, image_size
+    x = gb.placeholder("input", np.float32, [-1, d, s, s, in_ch],
+                       signature_name="input")
+    e1 = conv("enc1", x, in_ch, base)                           # d, s
+    e2 = conv("enc2", pool("pool1", e1), base, base * 2)        # d/2, s/2
+    bott = conv("bottleneck", pool("pool2", e2), base * 2, base * 4)
+    u1 = bn_relu("up1", deconv("up1", bott, base * 4, base * 2, 2,
+                               (d // 2, s // 2, s // 2), "VALID"), base * 2)
+    d1 = conv("dec1", concat("cat1", u1, e2), base * 4, base * 2)
+    u2 = deconv("up2", d1, base * 2, base, 3, (d, s, s), "SAME")
+    u2 = gb.node("BiasAdd", "up2/bias",
+                 [u2, gb.const("up2/b", (rng.standard_normal(base) * 0.1
+                                         ).astype(np.float32))], T=f32)
+    u2 = gb.node("Relu", "up2/relu", [u2], T=f32)
+    d2 = conv("dec2", concat("cat2", u2, e1), base * 2, base)
+    logits = gb.node("Conv3D", "head/conv",
+                     [d2, weight("head/w", (1, 1, 1, base, num_classes),
+                                 2 * base)],
+                     T=f32, strides=gb.a_ints([1] * 5),
+                     padding=gb.a_str("SAME"), data_format=gb.a_str("NDHWC"))
+    logits = gb.node("BiasAdd", "logits",
+                     [logits, gb.const("head/b", np.zeros(num_classes,
+                                                          np.float32))],
+                     T=f32)
+    probs = gb.node("Softmax", "probs", [logits], T=f32)
+    gb.mark_output("probs", probs)
+    gb.mark_output("logits", logits)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # repo writer
 # ---------------------------------------------------------------------------
 _BUILDERS = {
