@@ -26,6 +26,7 @@ sources = [
     os.path.join(CSRC, "ops", "attention.hip"),
     os.path.join(CSRC, "ops", "topk.hip"),
     os.path.join(CSRC, "ops", "reduce.hip"),
+    os.path.join(CSRC, "ops", "lstm.hip"),
     os.path.join(CSRC, "fastpath.cpp"),
     os.path.join(CSRC, "frontend.cpp"),
     os.path.join(CSRC, "rest_frontend.cpp"),

@@ -48,6 +48,7 @@ enum CallKind : int {
   K_SCATTER,
   K_RESIZE,
   K_ZERO_INSERT,
+  K_LSTM,
 };
 
 struct Call {
@@ -306,6 +307,19 @@ static void launch_call(const Call& c, hipStream_t s) {
                               int(I[2]), int(I[3]), int(I[4]), int(I[5]));
       break;
     }
+    case K_LSTM: {
+      // ptrs: [pre, W_h, wci|0, wcf|0, wco|0, h0|0, c0|0, cstate, h, cs|0]
+      // ints: [T, B, H, st_t, st_b, pre_t, pre_b]; floats: [cell_clip]
+      // (absent = 0, no clip). st_* are element strides of h / cs rows,
+      // pre_* row strides of pre
+      if (c.ptrs.size() != 10 || I.size() != 7)
+        throw std::runtime_error("lstm needs 10 ptrs and 7 ints");
+      launch_lstm(s, cp(0), cp(1), cp(2), cp(3), cp(4), cp(5), cp(6),
+                  reinterpret_cast<float*>(c.ptrs[7]), p(8), p(9), I[0], I[1],
+                  I[2], I[3], I[4], I[5], I[6],
+                  c.floats.empty() ? 0.f : c.floats[0]);
+      break;
+    }
     default:
       throw std::runtime_error("unknown call kind " +
                                std::to_string(c.kind));
@@ -487,6 +501,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("K_SCATTER") = int(tfsc::K_SCATTER);
   mod.attr("K_RESIZE") = int(tfsc::K_RESIZE);
   mod.attr("K_ZERO_INSERT") = int(tfsc::K_ZERO_INSERT);
+  mod.attr("K_LSTM") = int(tfsc::K_LSTM);
 
   py::class_<tfsc::CallTemplate>(mod, "CallTemplate")
       .def(py::init([](py::list calls) {
@@ -532,6 +547,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("reduce_cols_tx_max", &tfsc::reduce_cols_tx_max);
   mod.def("reduce_cols_wg_target", &tfsc::reduce_cols_wg_target);
   mod.def("set_reduce_thresholds", &tfsc::set_reduce_thresholds);
+  mod.def("lstm_resident_max_h", &tfsc::lstm_resident_max_h);
+  mod.def("set_lstm_resident_max_h", &tfsc::set_lstm_resident_max_h);
 
   register_fastpath(mod);
   register_frontend(mod);

@@ -298,4 +298,40 @@ void launch_attention(hipStream_t s, const ushort* Q, const ushort* K,
                       int64_t bias_sb = 0, int64_t bias_sh = 0,
                       int64_t bias_sq = 0);
 
+// Fused LSTM over a whole sequence (TF BlockLSTM / BlockLSTMV2, K_LSTM),
+// ops/lstm.hip. With the gates in the order (i, ci, f, o):
+//   z = pre[t, b] + h_{t-1} W_h
+//   i = s(z_i + c wci), f = s(z_f + c wcf), g = tanh(z_ci)
+//   c' = g i + c f, clamped to +-clip when clip > 0
+//   o = s(z_o + c' wco), h = o tanh(c')
+// `pre` is x W_x + b for every row, bf16 [rows][N], N = 64 * ceil(H / 16),
+// row (t, b) at row t * pre_t + b * pre_b. Column
+// (j / 16) * 64 + (j % 16) * 4 + gate holds that gate of unit j; columns of
+// units >= H are zero. W_h is [N][pad64(H)] in the same column order, K
+// zero-padded. wci / wcf / wco are [H] (all three or none), h0 / c0 [B][H]
+// (null: zero state). h and the optional cs are bf16, row (t, b) at element
+// t * st_t + b * st_b. The cell state stays f32 for the whole sequence; h
+// is rounded to bf16 once per step and that value is the next step's
+// operand. cstate is an f32 [B][H] scratch, re-initialised by every call.
+// H <= lstm_resident_max_h() runs one launch (one workgroup per 16 batch
+// rows, W_h resident in LDS); anything larger runs one launch per step.
+// Throws before any launch on T, B or H < 1, on a null pre, W_h, h or
+// cstate, on a partial peephole triple, and on strides that fail a
+// sufficient no-overlap test: with the axes ordered by stride, the smaller
+// one >= H and the larger one >= (n_small - 1) * small + H (time-major and
+// batch-major layouts pass; other interleavings are refused).
+void launch_lstm(hipStream_t s, const ushort* pre, const ushort* wh,
+                 const ushort* wci, const ushort* wcf, const ushort* wco,
+                 const ushort* h0, const ushort* c0, float* cstate,
+                 ushort* h, ushort* cs, int64_t T, int64_t B, int64_t H,
+                 int64_t st_t, int64_t st_b, int64_t pre_t, int64_t pre_b,
+                 float clip);
+// largest H served by the resident kernel. The default is what the LDS a
+// workgroup may allocate holds (W_h plus two h buffers, one 16-unit tile
+// per wave, at most 8 waves); set 0 to force the stepped kernel, a negative
+// value to restore the default. A measurement switch
+// (scripts/lstm_probe.py)
+int lstm_resident_max_h();
+void set_lstm_resident_max_h(int h);
+
 }  // namespace tfsc

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .planner import Plan, PlanOp, conv3d_transpose_phases
+from .planner import Plan, PlanOp, conv3d_transpose_phases, lstm_unpack
 
 
 def _act(x: np.ndarray, act: str) -> np.ndarray:
@@ -192,6 +192,8 @@ class CpuExecutor:
             self._pool3d(op, _get, vals)
         elif k == "conv3d_transpose":
             self._conv3d_transpose(op, _get, vals)
+        elif k == "lstm":
+            self._lstm(op, _get, vals)
         elif k == "global_mean":
             x = _get(op.inputs[0])
             y = x.mean(axis=(1, 2), keepdims=p.get("keep", False))
@@ -311,6 +313,46 @@ class CpuExecutor:
             vals[op.outputs[0]] = z
         else:
             raise ValueError(f"unknown plan op {k}")
+
+    def _lstm(self, op: PlanOp, _get, vals) -> None:
+        """The lstm op from its packed master weights (planner.lstm_pack),
+        gates (i, ci, f, o); see planner.lower_lstm for the inputs."""
+        p = op.params
+        H = p["H"]
+        sig = _UNARY["sigmoid"]
+        x = _get(op.inputs[0])
+        if p["x_batch_major"]:
+            x = x.transpose(1, 0, 2)                     # -> [T,B,I]
+        wx, wh, b = (_get(i) for i in op.inputs[1:4])
+        ni = 4
+        wci = wcf = wco = np.zeros(H, np.float32)
+        if p["peephole"]:
+            wci, wcf, wco = (_get(i) for i in op.inputs[4:7])
+            ni = 7
+        T, Bn = x.shape[:2]
+        h = c = np.zeros((Bn, H), np.float32)
+        if p["h0"]:
+            h = _get(op.inputs[ni])
+            ni += 1
+        if p["c0"]:
+            c = _get(op.inputs[ni])
+        pre = lstm_unpack(x @ wx + b, H)                 # [T,B,4,H]
+        whu = lstm_unpack(wh, H)                         # [H,4,H]
+        hs = np.empty((T, Bn, H), np.float32)
+        cs = np.empty((T, Bn, H), np.float32)
+        for t in range(T):
+            z = pre[t] + np.einsum("bk,kgj->bgj", h, whu)
+            i = sig(z[:, 0] + c * wci)
+            f = sig(z[:, 2] + c * wcf)
+            c = np.tanh(z[:, 1]) * i + c * f
+            if p["cell_clip"] > 0:
+                c = np.clip(c, -p["cell_clip"], p["cell_clip"])
+            h = sig(z[:, 3] + c * wco) * np.tanh(c)
+            hs[t], cs[t] = h, c
+        vals[op.outputs[0]] = hs.transpose(1, 0, 2).copy() \
+            if p["h_batch_major"] else hs
+        if p["cs"]:
+            vals[op.outputs[1]] = cs
 
     def _conv2d(self, op: PlanOp, _get, vals) -> None:
         x = _get(op.inputs[0])          # [N,H,W,C]

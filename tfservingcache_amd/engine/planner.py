@@ -213,6 +213,10 @@ class _Lowerer:
         # conv node name -> (x_ref, (bh, bw), pads, BatchToSpaceND node)
         # of a folded SpaceToBatchND / conv / BatchToSpaceND sandwich
         self.atrous: Dict[str, tuple] = {}
+        # BlockLSTM node name -> the Transpose(perm=[1,0,2]) node folded
+        # into its x input / its h output (match_lstm_transposes)
+        self.lstm_x_fold: Dict[str, g.NodeDef] = {}
+        self.lstm_h_fold: Dict[str, g.NodeDef] = {}
 
     # -- tensor bookkeeping ----------------------------------------------
     def new_tensor(self, shape: Shape, dtype: str, kind: str, name: str = "",
@@ -287,6 +291,10 @@ class _Lowerer:
         for nd in self.order:
             if nd.op == "SpaceToBatchND":
                 self.match_atrous_sandwich(nd)
+
+        for nd in self.order:
+            if nd.op in ("BlockLSTM", "BlockLSTMV2") and len(nd.input) == 9:
+                self.match_lstm_transposes(nd)
 
         for nd in self.order:
             if nd.name in self.pattern_emit:
@@ -417,6 +425,11 @@ class _Lowerer:
         if op in ("TopKV2", "TopK"):
             self.lower_topk(nd)
             return
+        if op in ("BlockLSTM", "BlockLSTMV2"):
+            self.lower_lstm(nd)
+            return
+        if op == "Fill" and self._is_lstm_zero_state(nd):
+            return          # read by lower_lstm as "zero state"; no tensor
         if op == "MatMul":
             self.lower_matmul(nd, out)
             return
@@ -1537,6 +1550,195 @@ class _Lowerer:
         idx = self.new_tensor(shape, "i32", "activation", f"{nd.name}:1")
         self.ops.append(PlanOp("topk_last", [x], [vals, idx], {"k": k}))
 
+    # -- BlockLSTM / BlockLSTMV2 -------------------------------------------
+    def _is_swap01(self, nd: Optional[g.NodeDef]) -> bool:
+        """nd is a Transpose with the constant perm [1, 0, 2]."""
+        if nd is None or nd.op != "Transpose" or len(nd.input) < 2:
+            return False
+        perm = self.const_value(nd.input[1])
+        return perm is not None and [int(p) for p in perm] == [1, 0, 2]
+
+    def _sig_output_names(self) -> set:
+        return {_tensor_name(ti.name)
+                for ti in self.signature.outputs.values()}
+
+    def _lstm_wants(self, nd: g.NodeDef, k: int) -> bool:
+        name = f"{nd.name}:{k}"
+        return bool(self.consumers.get(name)) or \
+            name in self._sig_output_names()
+
+    def match_lstm_transposes(self, nd: g.NodeDef) -> None:
+        """Fold the Transpose(perm=[1,0,2]) pair a batch-major model wraps
+        around a BlockLSTM into the op's strides. The one in front folds
+        when nothing but this node reads its data (Shape nodes, which
+        LSTMBlockFusedCell hangs on x for seq_len_max and the zero state,
+        read only its shape): its tensor is then registered for its shape
+        alone and no op produces it. The one behind folds when it is the
+        sole consumer of h and cs is not wanted (cs would share h's
+        strides)."""
+        tr = self.nodes.get(_node_of(nd.input[1]))
+        # a Transpose already folded as the previous layer's h output is
+        # that layer's (batch-major) output tensor: it stays x as it is
+        if self._is_swap01(tr) and \
+                all(tr is not t for t in self.lstm_h_fold.values()) and all(
+                c is nd or c.op == "Shape"
+                for c in self.consumers.get(f"{tr.name}:0", [])) and \
+                sum(1 for r in nd.input if _node_of(r) == tr.name) == 1 and \
+                f"{tr.name}:0" not in self._sig_output_names():
+            self.lstm_x_fold[nd.name] = tr
+            self.pattern_emit[tr.name] = (self._shape_only_transpose, (tr,))
+        h_name = f"{nd.name}:6"
+        cons = self.consumers.get(h_name, [])
+        if len(cons) == 1 and self._is_swap01(cons[0]) and \
+                _tensor_name(cons[0].input[0]) == h_name and \
+                h_name not in self._sig_output_names() and \
+                not self._lstm_wants(nd, 1):
+            self.lstm_h_fold[nd.name] = cons[0]
+            self.fused.add(cons[0].name)
+
+    def _shape_only_transpose(self, tr: g.NodeDef) -> None:
+        xs = self.shape_of(tr.input[0])
+        self.new_tensor((xs[1], xs[0], xs[2]), "f32", "activation",
+                        f"{tr.name}:0")
+
+    def _is_lstm_zero_state(self, fill: g.NodeDef) -> bool:
+        """A Fill(dims, 0) with constant dims whose every consumer is a
+        BlockLSTM's cs_prev / h_prev."""
+        cons = self.consumers.get(f"{fill.name}:0", [])
+        if not cons or len(fill.input) != 2:
+            return False
+        for c in cons:
+            if c.op not in ("BlockLSTM", "BlockLSTMV2") or any(
+                    _node_of(r) == fill.name and i not in (2, 3)
+                    for i, r in enumerate(c.input)):
+                return False
+        dims = self.const_value(fill.input[0])
+        val = self.const_value(fill.input[1])
+        return dims is not None and val is not None and \
+            np.asarray(val).size == 1 and \
+            float(np.asarray(val).reshape(-1)[0]) == 0.0
+
+    def lower_lstm(self, nd: g.NodeDef) -> None:
+        """BlockLSTM (TF1 LSTMBlockFusedCell) / BlockLSTMV2 -> one `lstm`
+        op: inputs seq_len_max, x [T,B,I], cs_prev, h_prev, w [I+H,4H],
+        wci, wcf, wco, b [4H]; outputs :6 (h) and :1 (cs), both [T,B,H].
+
+        Normalised here, once: the gate columns (BlockLSTM i,ci,f,o; V2
+        i,f,ci,o) to (i, ci, f, o), forget_bias (BlockLSTM only) into b's
+        f slice, and the column order of the kernel (lstm_pack). The op's
+        inputs are [x, W_x [I,N], W_h [H,N], b [N]] then wci, wcf, wco [H]
+        (peephole only), h0, c0 [B,H] (each only when it is not a zero
+        Fill). W_h is a rank-2 master, so the GEMM weight transform gives
+        the kernel its [N][pad64(H)] with no case of its own. Params: T,
+        I, H, cell_clip (0 = none), peephole, h0, c0, cs (the second
+        output exists), x_batch_major / h_batch_major (a folded
+        Transpose, match_lstm_transposes: x is [B,T,I] / h is [B,T,H]).
+        seq_len_max must fold to a constant >= T; the training
+        intermediates :0 :2 :3 :4 :5 are not produced."""
+        who = f"{nd.op} {nd.name}"
+        if len(nd.input) != 9:
+            raise PlanError(f"{who}: needs 9 inputs, has {len(nd.input)}")
+        v2 = nd.op == "BlockLSTMV2"
+        for k in (0, 2, 3, 4, 5):
+            if self._lstm_wants(nd, k):
+                raise PlanError(f"{who}: output :{k} is a training "
+                                f"intermediate; only :6 (h) and :1 (cs) "
+                                f"are served")
+        in_tr = self.lstm_x_fold.get(nd.name)
+        out_tr = self.lstm_h_fold.get(nd.name)
+        x = self.tid(in_tr.input[0] if in_tr is not None else nd.input[1])
+        xt = self.tensors[x]
+        xs = xt.shape
+        if len(xs) != 3 or xt.dtype != "f32":
+            raise PlanError(f"{who}: x must be f32 [T,B,I] (got {xs})")
+        T, Bd, I = (xs[1], xs[0], xs[2]) if in_tr is not None else xs
+        if is_sym(T) or is_sym(I):
+            raise PlanError(f"{who}: T and I must be concrete (x {xs})")
+        T, I = int(T), int(I)
+
+        w_v = self.const_value(nd.input[4])
+        if w_v is None:
+            raise PlanError(f"{who}: w {nd.input[4]} must be a constant")
+        w = np.asarray(w_v, dtype=np.float32)
+        if w.ndim != 2 or w.shape[1] % 4 or w.shape[1] == 0 or \
+                w.shape[0] != I + w.shape[1] // 4:
+            raise PlanError(f"{who}: w {w.shape} is not [I+H, 4H] for "
+                            f"I = {I}")
+        H = w.shape[1] // 4
+        b_v = self.const_value(nd.input[8])
+        if b_v is None or np.shape(b_v) != (4 * H,):
+            raise PlanError(f"{who}: b {nd.input[8]} must be a constant "
+                            f"[{4 * H}]")
+        order = [0, 2, 1, 3] if v2 else [0, 1, 2, 3]
+        w4 = w.reshape(I + H, 4, H)[:, order]
+        b4 = np.asarray(b_v, dtype=np.float32).reshape(4, H)[order].copy()
+        if not v2:
+            b4[2] += _attr_f(nd, "forget_bias", 1.0)
+        clip = max(float(_attr_f(nd, "cell_clip", 0.0 if v2 else 3.0)), 0.0)
+        peephole = _attr_b(nd, "use_peephole", False)
+
+        slm = self.const_value(nd.input[0])
+        if slm is None or np.asarray(slm).size != 1:
+            raise PlanError(f"{who}: seq_len_max {nd.input[0]} must fold "
+                            f"to a constant (dynamic lengths unsupported)")
+        slm = int(np.asarray(slm).reshape(-1)[0])
+        if slm < T:
+            raise PlanError(f"{who}: seq_len_max = {slm} < T = {T} "
+                            f"(truncated sequences unsupported)")
+
+        def weight(tag, arr):
+            return self.new_tensor(tuple(arr.shape), "f32", "weight",
+                                   f"{nd.name}/{tag}",
+                                   weight=np.ascontiguousarray(arr))
+
+        inputs = [x, weight("w_x", lstm_pack(w4[:I], H)),
+                  weight("w_h", lstm_pack(w4[I:], H)),
+                  weight("b", lstm_pack(b4, H))]
+        if peephole:
+            for tag, ref in zip(("wci", "wcf", "wco"), nd.input[5:8]):
+                v = self.const_value(ref)
+                if v is None or np.shape(v) != (H,):
+                    raise PlanError(f"{who}: {tag} {ref} must be a "
+                                    f"constant [{H}]")
+                inputs.append(weight(tag, np.asarray(v, np.float32)))
+        has = {}
+        for tag, ref in (("h0", nd.input[3]), ("c0", nd.input[2])):
+            src = self.nodes.get(_node_of(ref))
+            if src is not None and src.op == "Fill" and \
+                    self._is_lstm_zero_state(src):
+                dims = [int(d) for d in
+                        np.asarray(self.const_value(src.input[0])).reshape(-1)]
+                want = [-1 if is_sym(Bd) else int(Bd), H]
+                if dims != want:
+                    raise PlanError(f"{who}: {tag} Fill dims {dims} are "
+                                    f"not [B, H] = {want}")
+                has[tag] = False
+                continue
+            s_id = self.tid(ref)
+            st = self.tensors[s_id]
+            if st.dtype != "f32" or tuple(st.shape) != (Bd, H):
+                raise PlanError(f"{who}: {tag} {ref} must be f32 "
+                                f"[B, {H}] (got {st.shape})")
+            inputs.append(s_id)
+            has[tag] = True
+
+        if out_tr is not None:
+            h = self.new_tensor((Bd, T, H), "f32", "activation",
+                                f"{out_tr.name}:0")
+        else:
+            h = self.new_tensor((T, Bd, H), "f32", "activation",
+                                f"{nd.name}:6")
+        outputs = [h]
+        want_cs = self._lstm_wants(nd, 1)
+        if want_cs:
+            outputs.append(self.new_tensor((T, Bd, H), "f32", "activation",
+                                           f"{nd.name}:1"))
+        self.ops.append(PlanOp("lstm", inputs, outputs, {
+            "T": T, "I": I, "H": H, "cell_clip": clip,
+            "peephole": peephole, "h0": has["h0"], "c0": has["c0"],
+            "cs": want_cs, "x_batch_major": in_tr is not None,
+            "h_batch_major": out_tr is not None}))
+
     def lower_einsum(self, nd: g.NodeDef, out: str) -> None:
         """Einsum (transformer SavedModel exports). Supported family:
         2-operand contractions where the contracted indices are the
@@ -2114,6 +2316,34 @@ def conv3d_transpose_taps(trs, stride, c: int) -> int:
                for _p, taps, first in conv3d_transpose_phases(trs, stride)
                if taps)
     return -(-need // c)
+
+
+def lstm_cols(H: int) -> int:
+    """N, the width of an lstm op's packed gate axis: 64 columns (16
+    units x 4 gates) per tile of 16 hidden units."""
+    return (H + 15) // 16 * 64
+
+
+def lstm_pack(a: np.ndarray, H: int) -> np.ndarray:
+    """[..., 4, H] in gate order (i, ci, f, o) -> [..., N] in the LSTM
+    kernels' column order (csrc/ops/lstm.hip): column
+    (j // 16) * 64 + (j % 16) * 4 + gate holds that gate of unit j, so
+    the 4 gates x 16 units a workgroup computes are 64 adjacent columns
+    (adjacent rows of the transformed weight). Units H.. of the last
+    tile are zero: a padded unit has zero weights and bias, so its c and
+    h stay 0."""
+    tiles = (H + 15) // 16
+    p = np.zeros(a.shape[:-1] + (tiles * 16,), np.float32)
+    p[..., :H] = a
+    p = p.reshape(a.shape[:-2] + (4, tiles, 16))
+    return np.moveaxis(p, -3, -1).reshape(a.shape[:-2] + (tiles * 64,))
+
+
+def lstm_unpack(p: np.ndarray, H: int) -> np.ndarray:
+    """Inverse of lstm_pack: [..., N] -> [..., 4, H]."""
+    tiles = (H + 15) // 16
+    a = np.moveaxis(p.reshape(p.shape[:-1] + (tiles, 16, 4)), -1, -3)
+    return a.reshape(p.shape[:-1] + (4, tiles * 16))[..., :H]
 
 
 def _broadcast(sa: Sequence[Dim], sb: Sequence[Dim]) -> Shape:

@@ -1163,6 +1163,91 @@ def build_unet3d(depth=8, image_size=16, in_ch=3, base=16, num_classes=4,
 
 
 # ---------------------------------------------------------------------------
+# LSTM tagger (inference): the recurrent model family. A TF1 sequence
+# tagger as tf.contrib.rnn.LSTMBlockFusedCell exports it: batch-major ids,
+# an embedding lookup, Transpose to time-major, two fused block LSTMs (one
+# of each op spelling) whose seq_len_max and zero states hang on Shape(x),
+# Transpose back, and a per-token softmax.
+# ---------------------------------------------------------------------------
+def build_lstm_tagger(vocab=101, seq_len=12, d_embed=32, hidden=48,
+                      num_classes=7, cell_clip=0.25, seed=0):
+    """Input `input_ids` (int32 [B, seq_len]). Signature outputs: `probs`
+    [B, seq_len, num_classes] and `final_h` [B, hidden], the last step of
+    layer 2's h. Layer 1 is a BlockLSTMV2 (no peephole, no clip), layer 2
+    a BlockLSTM with peephole, forget_bias 1 and a cell_clip that binds."""
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32, i32, i64 = gb.a_type(1), gb.a_type(3), gb.a_type(9)
+    S, E, H = seq_len, d_embed, hidden
+
+    def c(name, v, dtype=np.float32):
+        return gb.const(name, np.asarray(v, dtype=dtype))
+
+    def W(name, shape, scale):
+        return c(name, rng.standard_normal(shape) * scale)
+
+    ids = gb.placeholder("input_ids", np.int32, [-1, S],
+                         signature_name="input_ids")
+    emb = gb.node("GatherV2", "embed",
+                  [W("embeddings", (vocab, E), 1.0), ids,
+                   c("gather_axis", 0, np.int32)], Tparams=f32, Tindices=i32)
+    swap = c("swap01", [1, 0, 2], np.int32)
+    x = gb.node("Transpose", "time_major", [emb, swap], T=f32, Tperm=i32)
+
+    shape = gb.node("Shape", "rnn/shape", [x], T=f32, out_type=i32)
+
+    def dim(name, k):
+        return gb.node("StridedSlice", name,
+                       [shape, c(f"{name}/b", [k], np.int32),
+                        c(f"{name}/e", [k + 1], np.int32),
+                        c(f"{name}/s", [1], np.int32)], T=i32, Index=i32,
+                       shrink_axis_mask=gb.a_int(1))
+
+    seq_len_max = gb.node("Cast", "rnn/seq_len_max", [dim("rnn/time", 0)],
+                          SrcT=i32, DstT=i64)
+    dims = gb.node("Pack", "rnn/state_dims",
+                   [dim("rnn/batch", 1), c("rnn/units", H, np.int32)],
+                   T=i32, N=gb.a_int(2), axis=gb.a_int(0))
+    zeros = gb.node("Fill", "rnn/zeros", [dims, c("rnn/zero", 0.0)], T=f32)
+
+    def lstm(op, name, inp, d_in, **attrs):
+        return gb.node(
+            op, name,
+            [seq_len_max, inp, zeros, zeros,
+             W(f"{name}/kernel", (d_in + H, 4 * H), (d_in + H) ** -0.5),
+             W(f"{name}/w_i_diag", (H,), 0.5),
+             W(f"{name}/w_f_diag", (H,), 0.5),
+             W(f"{name}/w_o_diag", (H,), 0.5),
+             W(f"{name}/bias", (4 * H,), 0.1)], T=f32, **attrs)
+
+    l1 = lstm("BlockLSTMV2", "rnn/layer1", x, E,
+              cell_clip=gb.a_float(0.0), use_peephole=gb.a_bool(False))
+    l2 = lstm("BlockLSTM", "rnn/layer2", f"{l1}:6", H,
+              forget_bias=gb.a_float(1.0), cell_clip=gb.a_float(cell_clip),
+              use_peephole=gb.a_bool(True))
+
+    h = gb.node("Transpose", "batch_major", [f"{l2}:6", swap], T=f32,
+                Tperm=i32)
+    flat = gb.node("Reshape", "tokens", [h, c("to_rows", [-1, H], np.int32)])
+    logits = gb.node("MatMul", "tag/mm",
+                     [flat, W("tag/w", (H, num_classes), H ** -0.5)], T=f32)
+    logits = gb.node("BiasAdd", "tag/bias",
+                     [logits, W("tag/b", (num_classes,), 0.1)], T=f32)
+    probs = gb.node("Softmax", "tag/softmax", [logits], T=f32)
+    probs = gb.node("Reshape", "probs",
+                    [probs, c("to_bsc", [-1, S, num_classes], np.int32)])
+    last = gb.node("StridedSlice", "final_h",
+                   [f"{l2}:6", c("last/b", [S - 1, 0, 0], np.int32),
+                    c("last/e", [S, 0, 0], np.int32),
+                    c("last/s", [1, 1, 1], np.int32)], T=f32, Index=i32,
+                   begin_mask=gb.a_int(6), end_mask=gb.a_int(6),
+                   shrink_axis_mask=gb.a_int(1))
+    gb.mark_output("probs", probs)
+    gb.mark_output("final_h", last)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # repo writer
 # ---------------------------------------------------------------------------
 _BUILDERS = {
