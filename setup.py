@@ -27,6 +27,7 @@ sources = [
     os.path.join(CSRC, "ops", "topk.hip"),
     os.path.join(CSRC, "ops", "reduce.hip"),
     os.path.join(CSRC, "ops", "lstm.hip"),
+    os.path.join(CSRC, "ops", "nms.hip"),
     os.path.join(CSRC, "fastpath.cpp"),
     os.path.join(CSRC, "frontend.cpp"),
     os.path.join(CSRC, "rest_frontend.cpp"),

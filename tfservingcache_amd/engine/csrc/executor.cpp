@@ -49,6 +49,7 @@ enum CallKind : int {
   K_RESIZE,
   K_ZERO_INSERT,
   K_LSTM,
+  K_NMS,
 };
 
 struct Call {
@@ -320,6 +321,27 @@ static void launch_call(const Call& c, hipStream_t s) {
                   c.floats.empty() ? 0.f : c.floats[0]);
       break;
     }
+    case K_NMS:
+      // select form, ptrs: [scores_cm, boxes, cls_score, cls_idx];
+      // ints: [B, N, C, q, P]; floats: [iou_thr, score_thr]. The gather
+      // form is ptrs: [slot, val, cls_idx, boxes, out_boxes, out_scores,
+      // out_classes, out_valid]; ints: [B, N, C, q, P, k, M, clip]
+      if (c.ptrs.size() == 4 && I.size() == 5 && c.floats.size() == 2) {
+        launch_nms_select(s, cp(0), cp(1), p(2),
+                          reinterpret_cast<int*>(c.ptrs[3]), I[0], I[1],
+                          I[2], I[3], I[4], c.floats[0], c.floats[1]);
+      } else if (c.ptrs.size() == 8 && I.size() == 8) {
+        launch_nms_gather(s, reinterpret_cast<const int*>(c.ptrs[0]), cp(1),
+                          reinterpret_cast<const int*>(c.ptrs[2]), cp(3),
+                          p(4), p(5), p(6),
+                          reinterpret_cast<int*>(c.ptrs[7]), I[0], I[1],
+                          I[2], I[3], I[4], I[5], I[6], I[7]);
+      } else {
+        throw std::runtime_error(
+            "nms select takes 4 ptrs, 5 ints and 2 floats, gather 8 ptrs "
+            "and 8 ints");
+      }
+      break;
     default:
       throw std::runtime_error("unknown call kind " +
                                std::to_string(c.kind));
@@ -502,6 +524,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.attr("K_RESIZE") = int(tfsc::K_RESIZE);
   mod.attr("K_ZERO_INSERT") = int(tfsc::K_ZERO_INSERT);
   mod.attr("K_LSTM") = int(tfsc::K_LSTM);
+  mod.attr("K_NMS") = int(tfsc::K_NMS);
 
   py::class_<tfsc::CallTemplate>(mod, "CallTemplate")
       .def(py::init([](py::list calls) {
@@ -549,6 +572,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("set_reduce_thresholds", &tfsc::set_reduce_thresholds);
   mod.def("lstm_resident_max_h", &tfsc::lstm_resident_max_h);
   mod.def("set_lstm_resident_max_h", &tfsc::set_lstm_resident_max_h);
+  mod.def("nms_lds_candidates", &tfsc::nms_lds_candidates);
+  mod.def("set_nms_lds_candidates", &tfsc::set_nms_lds_candidates);
 
   register_fastpath(mod);
   register_frontend(mod);

@@ -334,4 +334,42 @@ void launch_lstm(hipStream_t s, const ushort* pre, const ushort* wh,
 int lstm_resident_max_h();
 void set_lstm_resident_max_h(int h);
 
+// Per-class non-max suppression (TF CombinedNonMaxSuppression, K_NMS),
+// ops/nms.hip. Boxes are bf16 [B, N, q, 4] with q = 1 (shared by the
+// classes) or C, rows [y1, x1, y2, x2], 8-byte aligned.
+//
+// select: scores_cm is bf16 [B, C, N] (class-major). For every (image,
+// class) the boxes with score > score_thr (NaN fails) are visited by
+// descending score, equal scores (+0.0 == -0.0) by lower box index; one is
+// kept unless its IoU with a box kept earlier exceeds iou_thr, until P are
+// kept. IoU is f32: corners min/max-normalised, area <= 0 gives 0, else
+// inter / (a_i + a_j - inter), correctly rounded. The r-th kept box's
+// score bits go to cls_score[b, c * P + r] and its box index to cls_idx;
+// unused slots hold -inf and 0. One launch, one workgroup per (image,
+// class), nothing returns to the host.
+//
+// gather: slot / val [B, k] are the top-k of cls_score over its C * P
+// slots. Row m < k whose value is not -inf becomes box (clipped to [0, 1]
+// when clip), score and class slot / P as bf16; every other row of the M
+// is zeros; out_valid[b] counts the former.
+//
+// Both throw before any launch unless 1 <= N <= 2^19, C >= 1, q is 1 or C,
+// 1 <= P <= N, 0 <= iou_thr <= 1, 1 <= k <= min(M, C * P), clip is 0 or 1,
+// every pointer is set and the boxes are 8-byte aligned.
+void launch_nms_select(hipStream_t s, const ushort* scores_cm,
+                       const ushort* boxes, ushort* cls_score, int* cls_idx,
+                       int64_t B, int64_t N, int64_t C, int64_t q, int64_t P,
+                       float iou_thr, float score_thr);
+void launch_nms_gather(hipStream_t s, const int* slot, const ushort* val,
+                       const int* cls_idx, const ushort* boxes,
+                       ushort* out_boxes, ushort* out_scores,
+                       ushort* out_classes, int* out_valid, int64_t B,
+                       int64_t N, int64_t C, int64_t q, int64_t P, int64_t k,
+                       int64_t M, int64_t clip);
+// classes with at most this many candidates (<= 8192) run the greedy loop
+// out of LDS, the others stream scores and boxes from L2 under an LDS alive
+// mask; a measurement switch (scripts/nms_probe.py)
+int nms_lds_candidates();
+void set_nms_lds_candidates(int n);
+
 }  // namespace tfsc

@@ -45,7 +45,7 @@ KINDS = frozenset({
 # kinds no golden call template (tests/golden/call_templates) holds yet.
 # KINDS is exactly the set those templates reach; a kind moves there with
 # its golden case. _call accepts both sets, and nothing else reads this one
-KINDS_NO_GOLDEN = frozenset({"LSTM"})
+KINDS_NO_GOLDEN = frozenset({"LSTM", "NMS"})
 
 # plan ops that are one [rows, cols] kernel over the last axis
 _ROWWISE = {"softmax": "SOFTMAX", "reduce_mean_last": "MEAN_LAST",
@@ -301,6 +301,8 @@ class _Emitter:
                 P = topk_segments(rows, cols, op.params["k"])
                 if P > 1:
                     scratch_sizes[oi] = rows * P * op.params["k"] * 8
+            if op.kind == "combined_nms":
+                scratch_sizes[oi] = self._nms_scratch(op)[-1]
             if op.kind == "reduce":
                 # a split axis's partials: P f32 per output element
                 outer, red, inner = self._reduce_view(op)
@@ -426,6 +428,8 @@ class _Emitter:
                 self._c_conv3d_transpose(op, oi)
             elif k == "lstm":
                 self._c_lstm(op, oi)
+            elif k == "combined_nms":
+                self._c_combined_nms(op, oi)
             elif k == "batched_gemm":
                 self._c_bgemm(op)
             elif k == "attention":
@@ -883,6 +887,61 @@ class _Emitter:
                    [pre, (("gw", wh, False), 0), *peep, h0, c0,
                     _off(pre, c_off), self._ptr(op.outputs[0]), cs],
                    [T, Bn, H, *st, *pst], [float(p["cell_clip"])])
+
+    def _nms_scratch(self, op: PlanOp) -> Tuple[int, ...]:
+        """Byte offsets of (cls_score, cls_idx, slot, val, top-k partials)
+        inside a combined_nms op's scratch, and its size. The class-major
+        scores [B,C,N] bf16 sit at 0 (nothing when C == 1); cls_score bf16
+        and cls_idx i32 are [B, C*P]; slot i32 and val bf16 are the top-k
+        result [B, k]; the partials are topk_last's."""
+        p = op.params
+        nb = self.shapes[op.inputs[1]][0]
+        slots = p["c"] * p["per_class"]
+        k = min(p["max_total"], slots)
+        seg = topk_segments(nb, slots, k)
+        sizes = [nb * p["c"] * p["n"] * 2 if p["c"] > 1 else 0,
+                 nb * slots * 2, nb * slots * 4, nb * k * 4, nb * k * 2,
+                 nb * seg * k * 8 if seg > 1 else 0]
+        offs = [0]
+        for sz in sizes:
+            offs.append(offs[-1] + _pad256b(sz))
+        return tuple(offs[1:])
+
+    def _c_combined_nms(self, op: PlanOp, oi: int) -> None:
+        """TRANSPOSE (scores to class-major, skipped when C == 1), NMS
+        select, ARGMAX_LAST's top-k form over the C*P per-class slots, NMS
+        gather. Select, ptrs: [scores_cm, boxes, cls_score, cls_idx]; ints:
+        [B, N, C, q, P]; floats: [iou_thr, score_thr]. Gather, ptrs: [slot,
+        val, cls_idx, boxes, out_boxes, out_scores, out_classes, out_valid];
+        ints: [B, N, C, q, P, k, M, clip]."""
+        p = op.params
+        n, c, q, P, M = p["n"], p["c"], p["q"], p["per_class"], p["max_total"]
+        nb = self.shapes[op.inputs[1]][0]
+        if tuple(self.shapes[op.inputs[0]]) != (nb, n, q, 4) or \
+                tuple(self.shapes[op.inputs[1]]) != (nb, n, c):
+            raise RuntimeError(f"GPU combined_nms: bad params {p}")
+        boxes, scores = (self._ptr(i) for i in op.inputs)
+        base = self._scratch(oi)
+        o_score, o_idx, o_slot, o_val, o_part, _ = self._nms_scratch(op)
+        cls_score, cls_idx = _off(base, o_score), _off(base, o_idx)
+        slot, val = _off(base, o_slot), _off(base, o_val)
+        if c > 1:
+            self._call("TRANSPOSE", [scores, base],
+                       [3, nb, c, n, n * c, 1, c, nb * c * n])
+            scores = base
+        self._call("NMS", [scores, boxes, cls_score, cls_idx],
+                   [nb, n, c, q, P],
+                   [float(p["iou_thr"]), float(p["score_thr"])])
+        k = min(M, c * P)
+        seg = topk_segments(nb, c * P, k)
+        self._call("ARGMAX_LAST",
+                   [cls_score, slot, val,
+                    _off(base, o_part) if seg > 1 else None],
+                   [nb, c * P, k, seg])
+        self._call("NMS",
+                   [slot, val, cls_idx, boxes] +
+                   [self._ptr(o) for o in op.outputs],
+                   [nb, n, c, q, P, k, M, 1 if p["clip"] else 0])
 
     def _c_bgemm(self, op: PlanOp) -> None:
         p = op.params

@@ -105,6 +105,68 @@ def _resize(x, out_hw, mode, align_corners, half_pixel):
     return (top + (bot - top) * ly).astype(np.float32)
 
 
+def combined_nms(boxes, scores, per_class, max_total, iou_thr, score_thr,
+                 clip=True):
+    """TF CombinedNonMaxSuppression with the tie order pinned. boxes
+    [B,N,q,4] (q = 1 or C, rows y1,x1,y2,x2), scores [B,N,C]; `per_class`
+    is P = min(max_output_size_per_class, N) and `max_total` the output
+    rows M. Returns (boxes [B,M,4], scores [B,M], classes [B,M], all f32,
+    valid [B] i32), rows past the valid count zero.
+
+    Per image and class the boxes with score > score_thr (NaN fails) are
+    visited by descending score, equal scores by lower box index; one is
+    kept unless its IoU with an already kept box of the class is >
+    iou_thr, until P are kept. IoU is TF's CPU kernel's, in f32: corners
+    min/max-normalised, area <= 0 gives 0, else inter / (a_i + a_j -
+    inter). The image's kept (class, box) pairs, by descending score, then
+    lower class, then earlier kept, give the first M rows; the box leaves
+    as given, clipped to [0, 1] when `clip`."""
+    boxes = np.asarray(boxes, np.float32)
+    scores = np.asarray(scores, np.float32)
+    nb, n, c = scores.shape
+    q = boxes.shape[2]
+    f32 = np.float32
+    lo = np.minimum(boxes[..., :2], boxes[..., 2:])
+    hi = np.maximum(boxes[..., :2], boxes[..., 2:])
+    area = (hi[..., 0] - lo[..., 0]) * (hi[..., 1] - lo[..., 1])
+    out_b = np.zeros((nb, max_total, 4), f32)
+    out_s = np.zeros((nb, max_total), f32)
+    out_c = np.zeros((nb, max_total), f32)
+    valid = np.zeros((nb,), np.int32)
+    for b in range(nb):
+        kept = []                        # (-score, class, rank, box index)
+        for cl in range(c):
+            qi = 0 if q == 1 else cl
+            s = scores[b, :, cl]
+            live = np.flatnonzero(s > f32(score_thr))
+            live = live[np.argsort(-s[live], kind="stable")]
+            rank = 0
+            while live.size and rank < per_class:
+                i, live = live[0], live[1:]
+                kept.append((-s[i], cl, rank, i))
+                rank += 1
+                wh = np.maximum(
+                    np.minimum(hi[b, i, qi], hi[b, live, qi]) -
+                    np.maximum(lo[b, i, qi], lo[b, live, qi]), f32(0))
+                inter = wh[:, 0] * wh[:, 1]
+                ok = (area[b, i, qi] > 0) & (area[b, live, qi] > 0) & \
+                    (inter > 0)
+                union = area[b, i, qi] + area[b, live, qi] - inter
+                iou = np.where(ok, inter / np.where(ok, union, f32(1)),
+                               f32(0))
+                live = live[~(iou > f32(iou_thr))]
+        kept.sort()
+        kept = kept[:max_total]
+        valid[b] = len(kept)
+        for m_, (ns, cl, _rank, i) in enumerate(kept):
+            out_b[b, m_] = boxes[b, i, 0 if q == 1 else cl]
+            out_s[b, m_] = -ns
+            out_c[b, m_] = cl
+    if clip:
+        out_b = np.clip(out_b, f32(0), f32(1))
+    return out_b, out_s, out_c, valid
+
+
 class CpuExecutor:
     def __init__(self, plan: Plan):
         self.plan = plan
@@ -300,6 +362,12 @@ class CpuExecutor:
             idx = np.argsort(-x, axis=-1, kind="stable")[..., :p["k"]]
             vals[op.outputs[0]] = np.take_along_axis(x, idx, axis=-1)
             vals[op.outputs[1]] = idx.astype(np.int32)
+        elif k == "combined_nms":
+            res = combined_nms(_get(op.inputs[0]), _get(op.inputs[1]),
+                               p["per_class"], p["max_total"], p["iou_thr"],
+                               p["score_thr"], p["clip"])
+            for o, v in zip(op.outputs, res):
+                vals[o] = v
         elif k == "resize":
             vals[op.outputs[0]] = _resize(
                 _get(op.inputs[0]), p["out_hw"], p["mode"],

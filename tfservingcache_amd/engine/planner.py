@@ -428,6 +428,9 @@ class _Lowerer:
         if op in ("BlockLSTM", "BlockLSTMV2"):
             self.lower_lstm(nd)
             return
+        if op == "CombinedNonMaxSuppression":
+            self.lower_combined_nms(nd)
+            return
         if op == "Fill" and self._is_lstm_zero_state(nd):
             return          # read by lower_lstm as "zero state"; no tensor
         if op == "MatMul":
@@ -1549,6 +1552,82 @@ class _Lowerer:
         vals = self.new_tensor(shape, "f32", "activation", f"{nd.name}:0")
         idx = self.new_tensor(shape, "i32", "activation", f"{nd.name}:1")
         self.ops.append(PlanOp("topk_last", [x], [vals, idx], {"k": k}))
+
+    # most boxes per image: the N-bit alive mask of the streamed geometry
+    # is 64 KB of LDS (csrc/ops/nms.hip)
+    NMS_MAX_BOXES = 1 << 19
+    # class ids leave as bf16, which holds the integers up to 256
+    NMS_MAX_CLASSES = 256
+
+    def lower_combined_nms(self, nd: g.NodeDef) -> None:
+        """CombinedNonMaxSuppression(boxes [B,N,q,4], scores [B,N,C],
+        max_output_size_per_class, max_total_size, iou_threshold,
+        score_threshold) -> one `combined_nms` op with four outputs:
+        `name:0` nmsed_boxes [B,M,4], `name:1` nmsed_scores [B,M],
+        `name:2` nmsed_classes [B,M] (f32) and `name:3` valid_detections
+        [B] (i32). The sizes and thresholds must be constants, so every
+        shape is static. Semantics, ties included: executor_cpu.combined_nms."""
+        who = f"{nd.op} {nd.name}"
+        if len(nd.input) < 6:
+            raise PlanError(f"{who}: needs six inputs")
+        boxes, scores = self.tid(nd.input[0]), self.tid(nd.input[1])
+        bt, st = self.tensors[boxes], self.tensors[scores]
+        if bt.dtype != "f32" or st.dtype != "f32":
+            raise PlanError(f"{who}: only f32 boxes and scores supported")
+        consts = []
+        for ref, what in zip(nd.input[2:6],
+                             ("max_output_size_per_class", "max_total_size",
+                              "iou_threshold", "score_threshold")):
+            v = self.const_value(ref)
+            if v is None or np.asarray(v).size != 1:
+                raise PlanError(f"{who}: {what} must be a constant")
+            consts.append(np.asarray(v).reshape(-1)[0])
+        per_class, max_total = int(consts[0]), int(consts[1])
+        iou_thr, score_thr = float(consts[2]), float(consts[3])
+        if len(bt.shape) != 4 or len(st.shape) != 3 or \
+                bt.shape[0] != st.shape[0]:
+            raise PlanError(f"{who}: boxes {bt.shape} / scores {st.shape} "
+                            f"are not [B,N,q,4] / [B,N,C]")
+        n, c = st.shape[1], st.shape[2]
+        if is_sym(n) or is_sym(c) or n < 1 or c < 1:
+            raise PlanError(f"{who}: N and C must be concrete (scores "
+                            f"{st.shape})")
+        q = bt.shape[2]
+        if bt.shape[3] != 4:
+            raise PlanError(f"{who}: the last dim of boxes {bt.shape} "
+                            f"must be 4")
+        if bt.shape[1] != n or q not in (1, c):
+            raise PlanError(f"{who}: boxes {bt.shape} need N = {n} and "
+                            f"q in (1, {c})")
+        if n > self.NMS_MAX_BOXES:
+            raise PlanError(f"{who}: N = {n} above {self.NMS_MAX_BOXES}")
+        if c > self.NMS_MAX_CLASSES:
+            raise PlanError(f"{who}: C = {c} above {self.NMS_MAX_CLASSES} "
+                            f"(class ids are bf16)")
+        if per_class < 1 or max_total < 1:
+            raise PlanError(f"{who}: max_output_size_per_class = "
+                            f"{per_class} and max_total_size = {max_total} "
+                            f"must be >= 1")
+        if not 0.0 <= iou_thr <= 1.0:
+            raise PlanError(f"{who}: iou_threshold {iou_thr} outside [0, 1]")
+        if np.isnan(score_thr):
+            raise PlanError(f"{who}: score_threshold is NaN")
+        P = min(per_class, n)
+        M = min(max_total, per_class * c) \
+            if _attr_b(nd, "pad_per_class", False) else max_total
+        if min(M, c * P) > self.TOPK_MAX_K:
+            raise PlanError(f"{who}: min(max_total, C * per_class) = "
+                            f"{min(M, c * P)} above {self.TOPK_MAX_K}")
+        b = st.shape[0]
+        outs = [self.new_tensor(shape, dt, "activation", f"{nd.name}:{i}")
+                for i, (shape, dt) in enumerate(
+                    (((b, M, 4), "f32"), ((b, M), "f32"), ((b, M), "f32"),
+                     ((b,), "i32")))]
+        self.ops.append(PlanOp(
+            "combined_nms", [boxes, scores], outs,
+            {"n": n, "c": c, "q": q, "per_class": P, "max_total": M,
+             "iou_thr": iou_thr, "score_thr": score_thr,
+             "clip": _attr_b(nd, "clip_boxes", True)}))
 
     # -- BlockLSTM / BlockLSTMV2 -------------------------------------------
     def _is_swap01(self, nd: Optional[g.NodeDef]) -> bool:

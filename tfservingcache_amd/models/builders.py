@@ -1248,6 +1248,127 @@ def build_lstm_tagger(vocab=101, seq_len=12, d_embed=32, hidden=48,
 
 
 # ---------------------------------------------------------------------------
+# SSD-style detector (inference): the object-detection model family. A
+# strided conv backbone, two feature levels with a class head and a box
+# head each, Reshape / ConcatV2 to [B,N,C] and [B,N,4], Sigmoid scores, the
+# box decode against constant anchors (centre = t_yx * anchor_hw +
+# anchor_yx, size = exp(t_hw) * anchor_hw) and CombinedNonMaxSuppression,
+# the batched fixed-shape NMS of TF serving exports.
+# ---------------------------------------------------------------------------
+def build_ssd_detector(image_size=64, num_classes=3, anchors_per_cell=2,
+                       max_per_class=10, max_total=20, iou_threshold=0.45,
+                       score_threshold=0.5, pad_per_class=False,
+                       clip_boxes=True, seed=0):
+    """Input `input` [B, s, s, 3], s a multiple of 16. Levels at s/8 and
+    s/16, so N = anchors_per_cell * ((s/8)^2 + (s/16)^2). Signature
+    outputs: `nmsed_boxes` [B,M,4], `nmsed_scores` [B,M], `nmsed_classes`
+    [B,M], `valid_detections` [B] (i32), and the NMS inputs `boxes`
+    [B,N,1,4] and `scores` [B,N,C]."""
+    if image_size % 16:
+        raise ValueError("image_size must be a multiple of 16")
+    rng = np.random.default_rng(seed)
+    gb = GraphBuilder()
+    f32, i32 = gb.a_type(1), gb.a_type(3)
+    A, C = anchors_per_cell, num_classes
+
+    def c(name, v, dtype=np.float32):
+        return gb.const(name, np.asarray(v, dtype=dtype))
+
+    def conv(name, x, cin, cout, stride, relu=True, scale=1.0):
+        w = c(f"{name}/w", rng.standard_normal((3, 3, cin, cout))
+              * np.sqrt(2.0 / (9 * cin)) * scale)
+        b = c(f"{name}/b", rng.standard_normal(cout) * 0.1)
+        h = gb.node("Conv2D", f"{name}/conv", [x, w], T=f32,
+                    strides=gb.a_ints([1, stride, stride, 1]),
+                    padding=gb.a_str("SAME"), data_format=gb.a_str("NHWC"))
+        h = gb.node("BiasAdd", f"{name}/bias", [h, b], T=f32)
+        return gb.node("Relu", f"{name}/relu", [h], T=f32) if relu else h
+
+    s = image_size
+    x = gb.placeholder("input", np.float32, [-1, s, s, 3],
+                       signature_name="input")
+    h = conv("stem", x, 3, 16, 2)
+    h = conv("block1", h, 16, 32, 2)
+    f1 = conv("block2", h, 32, 32, 2)          # s/8
+    f2 = conv("block3", f1, 32, 64, 2)         # s/16
+
+    cls_parts, box_parts, anchors = [], [], []
+    for li, (feat, ch, hw) in enumerate(((f1, 32, s // 8), (f2, 64, s // 16))):
+        n_l = hw * hw * A
+        cls = conv(f"head{li}/cls", feat, ch, A * C, 1, relu=False, scale=3.0)
+        box = conv(f"head{li}/box", feat, ch, A * 4, 1, relu=False)
+        cls_parts.append(gb.node(
+            "Reshape", f"head{li}/cls_flat",
+            [cls, c(f"head{li}/cls_shape", [-1, n_l, C], np.int32)], T=f32))
+        box_parts.append(gb.node(
+            "Reshape", f"head{li}/box_flat",
+            [box, c(f"head{li}/box_shape", [-1, n_l, 4], np.int32)], T=f32))
+        # anchors in (y, x, anchor) order like the head's channels: centres
+        # on the cell grid, sides 2.5 and 3.5 cells so neighbours overlap
+        cy, cx, a = np.meshgrid(np.arange(hw), np.arange(hw), np.arange(A),
+                                indexing="ij")
+        side = (2.5 + a) / hw
+        anchors.append(np.stack([(cy + 0.5) / hw, (cx + 0.5) / hw,
+                                 side, side * (1.0 + 0.25 * a)],
+                                -1).reshape(n_l, 4))
+    anchors = np.concatenate(anchors)
+    N = anchors.shape[0]
+
+    axis1 = c("concat_axis", 1, np.int32)
+    logits = gb.node("ConcatV2", "cls_logits", cls_parts + [axis1], T=f32,
+                     N=gb.a_int(2), Tidx=i32)
+    scores = gb.node("Sigmoid", "scores", [logits], T=f32)
+    deltas = gb.node("ConcatV2", "box_deltas", box_parts + [axis1], T=f32,
+                     N=gb.a_int(2), Tidx=i32)
+
+    def cols(name, lo, hi):
+        return gb.node("StridedSlice", name,
+                       [deltas, c(f"{name}/b", [0, 0, lo], np.int32),
+                        c(f"{name}/e", [0, 0, hi], np.int32),
+                        c(f"{name}/s", [1, 1, 1], np.int32)], T=f32,
+                       Index=i32, begin_mask=gb.a_int(3),
+                       end_mask=gb.a_int(3))
+
+    anchor_yx = c("anchors/yx", anchors[:, :2])
+    anchor_hw = c("anchors/hw", anchors[:, 2:])
+    t_yx = gb.node("Mul", "decode/t_yx",
+                   [cols("decode/yx", 0, 2), c("decode/yx_scale", 0.1)], T=f32)
+    t_hw = gb.node("Mul", "decode/t_hw",
+                   [cols("decode/hw", 2, 4), c("decode/hw_scale", 0.2)], T=f32)
+    centre = gb.node("Add", "decode/centre",
+                     [gb.node("Mul", "decode/shift", [t_yx, anchor_hw], T=f32),
+                      anchor_yx], T=f32)
+    size = gb.node("Mul", "decode/size",
+                   [gb.node("Exp", "decode/exp", [t_hw], T=f32), anchor_hw],
+                   T=f32)
+    corners = [gb.node("Add", f"decode/{nm}",
+                       [centre, gb.node("Mul", f"decode/{nm}_half",
+                                        [size, c(f"decode/{nm}_k", k)],
+                                        T=f32)], T=f32)
+               for nm, k in (("min", -0.5), ("max", 0.5))]
+    boxes = gb.node("ConcatV2", "decode/corners",
+                    corners + [c("decode/axis", 2, np.int32)], T=f32,
+                    N=gb.a_int(2), Tidx=i32)
+    boxes = gb.node("Reshape", "boxes",
+                    [boxes, c("boxes_shape", [-1, N, 1, 4], np.int32)], T=f32)
+
+    nms = gb.node("CombinedNonMaxSuppression", "nms",
+                  [boxes, scores,
+                   c("nms/max_per_class", max_per_class, np.int32),
+                   c("nms/max_total", max_total, np.int32),
+                   c("nms/iou_threshold", iou_threshold),
+                   c("nms/score_threshold", score_threshold)],
+                  pad_per_class=gb.a_bool(pad_per_class),
+                  clip_boxes=gb.a_bool(clip_boxes))
+    for i, alias in enumerate(("nmsed_boxes", "nmsed_scores",
+                               "nmsed_classes", "valid_detections")):
+        gb.mark_output(alias, f"{nms}:{i}")
+    gb.mark_output("boxes", boxes)
+    gb.mark_output("scores", scores)
+    return gb.build()
+
+
+# ---------------------------------------------------------------------------
 # repo writer
 # ---------------------------------------------------------------------------
 _BUILDERS = {
