@@ -20,6 +20,7 @@ CSRC = os.path.join(ROOT, "tfservingcache_amd", "engine", "csrc")
 sources = [
     os.path.join(CSRC, "executor.cpp"),
     os.path.join(CSRC, "ops", "ops_memory.hip"),
+    os.path.join(CSRC, "ops", "weight_layout.hip"),
     os.path.join(CSRC, "ops", "gemm.hip"),
     os.path.join(CSRC, "ops", "gemm_fp8.hip"),
     os.path.join(CSRC, "ops", "conv.hip"),

@@ -562,6 +562,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             return std::unique_ptr<ExecPlan>(t.instantiate(ws, bases));
           });
 
+  // one launch on the current stream (engine/gpu.py
+  // try_restore_transforms); pointers are device addresses
+  mod.def("weight_layout",
+          [](uintptr_t blob, uintptr_t arena, uintptr_t table, int n_entries,
+             uintptr_t tile_start, int total_tiles) {
+            hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+            tfsc::launch_weight_layout(
+                s, reinterpret_cast<const ushort*>(blob),
+                reinterpret_cast<uint8_t*>(arena),
+                reinterpret_cast<const tfsc::LayoutEntry*>(table), n_entries,
+                reinterpret_cast<const int*>(tile_start), total_tiles);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess)
+              throw std::runtime_error(
+                  std::string("weight_layout launch failed: ") +
+                  hipGetErrorString(e));
+          },
+          py::call_guard<py::gil_scoped_release>());
+
   mod.def("topk_sort_max_cols", &tfsc::topk_sort_max_cols);
   mod.def("set_topk_sort_max_cols", &tfsc::set_topk_sort_max_cols);
   mod.def("conv_dilated_skip", &tfsc::conv_dilated_skip);

@@ -129,6 +129,39 @@ void set_reduce_thresholds(int wave_max_cols, int cols_tx_max,
 void launch_bf16_to_f32(hipStream_t s, const ushort* x, float* y,
                         int64_t n);
 
+// One region of a model's transform arena as a padded 2-D transpose of a
+// slot of the bf16 master blob (ops/weight_layout.hip; the table is built
+// by engine/emit.py weight_layout_table, whose LAYOUT_ENTRY_DTYPE mirrors
+// this struct). The slot is a row-major [rin][cin] matrix at element
+// src_off of the blob; the region starts at byte dst_off of the arena.
+//   transpose == 0: dst [rin][kp], dst[r][k] = src[r][k], 0 for k >= cin
+//     (gemm_weight with trans_b: a row copy with pad).
+//   transpose == 1: dst [cin][kp], dst[j][k] = src[q * c_src + c][j] with
+//     k = q * c_dst + c, 0 when c >= c_src or the source row is >= rin
+//     (conv_weight and gemm_weight without trans_b: c_src == c_dst;
+//     conv_weight_cpad: c_src = C, c_dst = c8, zeros between).
+// kp is a multiple of 64, at least the widened row count.
+struct LayoutEntry {
+  int64_t src_off;
+  int64_t dst_off;
+  int32_t rin, cin;
+  int32_t c_src, c_dst;
+  int32_t transpose;
+  int32_t kp;
+};
+// Lays out every entry in one launch: one workgroup per 64x64 destination
+// tile, tile_start_dev [n_entries + 1] the prefix sum of tiles per entry
+// (every entry has at least one), total_tiles its last element. Writes
+// all rows * kp * 2 bytes of each entry and nothing else. 16-byte accesses
+// where an address is 16-byte aligned, element accesses elsewhere. The
+// table lives on the device and is not checked here: emit.py
+// check_layout_table bounds it against the blob and the arena. Throws
+// before the launch on a null pointer, n_entries < 1 or
+// total_tiles < n_entries.
+void launch_weight_layout(hipStream_t s, const ushort* blob, uint8_t* arena,
+                          const LayoutEntry* table_dev, int n_entries,
+                          const int* tile_start_dev, int total_tiles);
+
 // GEMM: C[M,N] = act(A[M,K] @ B[K,N] + bias [+ residual]).
 // A row-major bf16, B row-major bf16 (pre-transposed at load if the graph
 // wanted B^T), C bf16. f32 accumulate via MFMA.

@@ -200,6 +200,107 @@ def blob_layout(plan: Plan) -> BlobLayout:
     return BlobLayout(slots, total, int_idx)
 
 
+# One transform-arena region as a padded 2-D transpose of a blob slot:
+# csrc/kernels.h LayoutEntry, field for field (40 bytes, no padding).
+LAYOUT_ENTRY_DTYPE = np.dtype([
+    ("src_off", "<i8"), ("dst_off", "<i8"), ("rin", "<i4"), ("cin", "<i4"),
+    ("c_src", "<i4"), ("c_dst", "<i4"), ("transpose", "<i4"), ("kp", "<i4")])
+LAYOUT_TILE = 64
+
+
+def _layout_entry(plan: Plan, layout: BlobLayout, key: tuple):
+    """(src_off, rin, cin, c_src, c_dst, transpose, kp, dst_rows) of the
+    region `key` when it is a re-layout of a blob slot (the "gw" and "cw"
+    regions of engine/gpu.py), else None."""
+    if key[0] not in ("gw", "cw") or key[1] not in layout.slots:
+        return None
+    shape = tuple(plan.tensors[key[1]].weight.shape)
+    src_off = layout.slots[key[1]][0]
+    if key[0] == "gw" and len(key) == 3 and len(shape) == 2:
+        if key[2]:                      # stored [N, K]: copy, pad K
+            rin, cin = shape
+            ent = (src_off, rin, cin, 1, 1, 0, _pad64(cin), rin)
+        else:                           # [K, N] -> [N][pad64(K)]
+            rin, cin = shape
+            ent = (src_off, rin, cin, rin, rin, 1, _pad64(rin), cin)
+    elif key[0] == "cw" and len(shape) == 4 and len(key) in (2, 4):
+        R, S, C, Kc = shape
+        rin = R * S * C
+        if len(key) == 2:               # [R*S*C, K] -> [K][pad64(R*S*C)]
+            ent = (src_off, rin, Kc, rin, rin, 1, _pad64(rin), Kc)
+        elif key[2] == "cpad" and key[3] >= C:
+            ent = (src_off, rin, Kc, C, key[3], 1,
+                   _pad64(R * S * key[3]), Kc)
+        else:
+            return None
+    else:
+        return None
+    if min(ent[1], ent[2], ent[3]) < 1 or max(ent[1:]) >= 1 << 31:
+        return None
+    return ent
+
+
+def weight_layout_table(plan: Plan, entries):
+    """The descriptor table of ops/weight_layout.hip for a transform
+    arena whose regions are `entries` [(key, byte offset, nbytes, ...)]:
+    (table, tile_start, covered). table is a LAYOUT_ENTRY_DTYPE array with
+    one row per bf16 region that is a pure re-layout of a blob slot
+    (conv_weight, conv_weight_cpad, gemm_weight), tile_start [n + 1] int32
+    the prefix sum of their 64x64 destination tiles, covered the set of
+    their keys. Regions outside it (int weights, fp8 bytes and scales)
+    stay a host copy. Plan-deterministic: shapes and blob_layout only."""
+    layout = blob_layout(plan)
+    rows, starts, covered = [], [0], set()
+    for e in entries:
+        key, off, nb = tuple(e[0]), e[1], e[2]
+        ent = _layout_entry(plan, layout, key)
+        if ent is None or ent[7] * ent[6] * 2 != nb:
+            continue
+        rows.append((ent[0], off) + ent[1:7])
+        starts.append(starts[-1] + -(-ent[7] // LAYOUT_TILE) *
+                      (ent[6] // LAYOUT_TILE))
+        covered.add(key)
+    if starts[-1] >= 1 << 31:
+        return (np.zeros(0, LAYOUT_ENTRY_DTYPE), np.zeros(1, np.int32),
+                set())
+    return (np.array(rows, dtype=LAYOUT_ENTRY_DTYPE),
+            np.array(starts, dtype=np.int32), covered)
+
+
+def check_layout_table(table, tile_start, blob_elems: int,
+                       arena_bytes: int) -> None:
+    """Raises ValueError unless every entry reads inside a blob of
+    blob_elems elements, writes inside an arena of arena_bytes bytes
+    without touching another entry, and tile_start is the prefix sum of
+    the entries' tiles. The kernel trusts its table; this is the check."""
+    if len(tile_start) != len(table) + 1 or tile_start[0] != 0:
+        raise ValueError("tile_start does not match the table")
+    spans = []
+    for i, e in enumerate(table):
+        rin, cin, kp = int(e["rin"]), int(e["cin"]), int(e["kp"])
+        c_src, c_dst = int(e["c_src"]), int(e["c_dst"])
+        tr = int(e["transpose"])
+        if min(rin, cin, c_src) < 1 or c_dst < c_src or tr not in (0, 1):
+            raise ValueError(f"layout entry {i}: bad extents")
+        wide = -(-rin // c_src) * c_dst if tr else cin
+        drows = cin if tr else rin
+        if kp % LAYOUT_TILE or kp < wide or (not tr and c_src != c_dst):
+            raise ValueError(f"layout entry {i}: bad row length {kp}")
+        src, dst = int(e["src_off"]), int(e["dst_off"])
+        if src < 0 or src + rin * cin > blob_elems:
+            raise ValueError(f"layout entry {i} reads outside the blob")
+        if dst < 0 or dst % 256 or dst + drows * kp * 2 > arena_bytes:
+            raise ValueError(f"layout entry {i} writes outside the arena")
+        tiles = -(-drows // LAYOUT_TILE) * (kp // LAYOUT_TILE)
+        if int(tile_start[i + 1]) - int(tile_start[i]) != tiles:
+            raise ValueError(f"layout entry {i}: tile_start is off")
+        spans.append((dst, dst + drows * kp * 2))
+    spans.sort()
+    for (_a0, a1), (b0, _b1) in zip(spans, spans[1:]):
+        if b0 < a1:
+            raise ValueError("layout entries overlap in the arena")
+
+
 @dataclass
 class Template:
     """Everything a context of one (plan, bucket, dtype) needs besides

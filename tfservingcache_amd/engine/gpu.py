@@ -9,7 +9,8 @@ template memory (all ahead of the hot path):
     weights pre-transposed to [N][K] bf16 with K zero-padded to a
     multiple of 64 so both MFMA fragments read contiguously along K
     (see csrc/ops/gemm.hip), fp8 GEMM weights with row scales — computed
-    on first use or restored from the plan's pinned transform arena;
+    on first use, or laid out from the blob by ops/weight_layout.hip on
+    a repeat load of the plan (the transform arena);
   * per-batch-bucket ExecContexts: a workspace arena, the template's
     region keys resolved to base addresses, the calls rebased by
     ext.instantiate_plan; optionally hipGraph-captured;
@@ -31,8 +32,9 @@ import warnings
 
 import numpy as np
 
-from .emit import (WS, _pad64, _pad128, _pad256b, blob_layout,
-                   build_template)
+from .emit import (LAYOUT_ENTRY_DTYPE, WS, _pad64, _pad128, _pad256b,
+                   blob_layout, build_template, check_layout_table,
+                   weight_layout_table)
 from .planner import Plan, is_sym, resolve_dim
 
 # weight arrays from memory-mapped SavedModels are read-only; we only
@@ -308,24 +310,66 @@ def _get_upload_stream(torch, device: str):
 #    offsets/scratch and the kernel calls with every pointer written as
 #    (region key, offset); every context is instantiated from it by
 #    pure pointer relocation, and models sharing the plan share it;
-#  * the TRANSFORM ARENA caches the transformed weight bytes
-#    (pre-transposed GEMM/conv layouts, fp8 quantized weights) in
-#    pinned host memory; a new model restores them with ONE DMA into a
-#    device arena and views at recorded offsets — no per-layer
-#    transform compute, and every transform lands at a deterministic
-#    arena offset (which is what makes call relocation possible).
+#  * the TRANSFORM ARENA records where every transformed weight
+#    (pre-transposed GEMM/conv layouts, fp8 quantized weights) lives in
+#    one device arena; a new model fills its arena with one launch of
+#    the weight-layout kernel over the master blob it uploaded (the
+#    bf16 layouts are re-layouts of blob bytes) plus a DMA of the few
+#    regions kept in pinned host memory because they are not — no
+#    per-layer transform compute, and every transform lands at a
+#    deterministic arena offset (which is what makes call relocation
+#    possible).
 # ---------------------------------------------------------------------------
 _TMPL_CAP = 64          # templates are ~100 KB of host data each
-_ARENA_CAP = 4          # arenas pin ~50 MB of host RAM each (like the
-                        # blob cache: only the hottest plan contents)
+_ARENA_CAP = 4          # like the blob cache, which a restore needs:
+                        # only the hottest plan contents (a full pinned
+                        # snapshot, TFSC_GPU_LAYOUT=off, is ~50 MB each)
 _tmpl_lock = threading.Lock()
 _ctx_templates: Dict[tuple, tuple] = {}     # (id(plan),bucket,dtype) ->
                                             # (plan, (Template,
                                             #         ext.CallTemplate))
 _tmpl_order: List[tuple] = []
 _transform_arenas: Dict[tuple, tuple] = {}  # (id(plan),dtype) ->
-                                            # (plan, entries, pinned)
+                                            # (plan, entries, _ArenaHost)
 _arena_order: List[tuple] = []
+
+
+class _ArenaHost:
+    """What a repeat load needs besides the master blob to fill a device
+    arena of `total` bytes. Regions that are re-layouts of blob slots
+    (bf16 conv / GEMM weights) are a descriptor table for
+    ops/weight_layout.hip: `table` holds LayoutEntry rows then tile_start
+    in one byte array, uploaded once per device (`table_on`). Everything
+    else (int weights, fp8 bytes and scales) is `pinned`, the contiguous
+    arena spans [(arena offset, pinned offset, nbytes)] packed into pinned
+    memory and DMA'd. With TFSC_GPU_LAYOUT=off at publish time the table
+    is empty and one span covers the whole arena."""
+
+    def __init__(self, total, pinned, spans, table, n_entries, total_tiles):
+        self.total = total
+        self.pinned = pinned
+        self.spans = spans
+        self.table = table
+        self.n_entries = n_entries
+        self.total_tiles = total_tiles
+        self._dev: Dict[str, object] = {}
+
+    def table_on(self, torch, device: str):
+        """The table on `device`; call inside capture_guard.unsafe_host_op
+        (the first call per device is a blocking pageable copy)."""
+        t = self._dev.get(device)
+        if t is None:
+            t = torch.from_numpy(self.table).to(device)
+            self._dev[device] = t
+        return t
+
+
+def gpu_layout_enabled() -> bool:
+    """TFSC_GPU_LAYOUT=off publishes arenas as full pinned snapshots (the
+    two-DMA repeat load), for A/B runs. Read when an arena is published."""
+    import os as _os
+    return _os.environ.get("TFSC_GPU_LAYOUT", "on").lower() not in (
+        "off", "0", "no")
 
 
 def _get_ctx_template(plan, bucket: int, dtype: str):
@@ -593,12 +637,15 @@ class GpuModel:
         import time as _time
         t0 = _time.monotonic()
         self._upload_pending = False
+        # whether this load's arena came from the weight-layout kernel
+        self.restored_by_kernel = False
         with torch.cuda.device(device):
             self._upload_weights()
             restored = self.try_restore_transforms()
             if self._upload_pending or restored:
-                # one sync covers both async DMAs (master blob +
-                # transform arena) on the shared upload stream. MUST be
+                # one sync covers the async work on the shared upload
+                # stream (master blob DMA, then the arena's layout
+                # kernel and remainder DMA). MUST be
                 # guard-serialized: a stream sync concurrent with
                 # another thread's capture invalidates the capture (the
                 # 100-step soak reproduced hipErrorStreamCapture*
@@ -929,9 +976,14 @@ class GpuModel:
         raise KeyError(f"unknown weight region {key}")
 
     def publish_transform_arena(self) -> None:
-        """Snapshot this model's transformed weights into a pinned host
-        arena keyed by the (content-deduplicated) plan, so later models
-        restore them with one DMA instead of per-layer transforms."""
+        """Record the arena layout of this model's transformed weights,
+        keyed by the (content-deduplicated) plan, so later models fill a
+        device arena without per-layer transforms. The bf16 conv / GEMM
+        layouts are pure re-layouts of the master blob every load uploads
+        anyway: for them only a descriptor table is kept (built from
+        shapes, uploaded here once) and a repeat load runs
+        ops/weight_layout.hip over its own blob. Only what cannot be
+        derived that way is snapshotted into pinned memory."""
         torch, _ = _load_backend()
         if _get_transform_arena(self.plan, self.dtype) is not None:
             return
@@ -944,34 +996,83 @@ class GpuModel:
             off = _pad256b(off + nb)
         if off == 0:
             return
+        table = np.zeros(0, LAYOUT_ENTRY_DTYPE)
+        tile_start = np.zeros(1, np.int32)
+        covered = set()
+        if gpu_layout_enabled() and \
+                getattr(self, "_weight_blob", None) is not None:
+            table, tile_start, covered = weight_layout_table(
+                self.plan, [e for e in entries
+                            if e[3] == torch.bfloat16])
+            check_layout_table(table, tile_start,
+                               self._weight_blob.numel(), off)
+        # contiguous runs of the regions that stay a host copy
+        spans = []              # [arena offset, pinned offset, nbytes]
+        pinned_at = {}          # key -> pinned offset of its bytes
+        p_off = 0
+        for key, o, nb, _dt, _shape in entries:
+            if key in covered:
+                continue
+            if not spans or spans[-1][0] + spans[-1][2] != o:
+                spans.append([o, p_off, 0])
+            pinned_at[key] = p_off
+            p_off += _pad256b(nb)
+            spans[-1][2] = p_off - spans[-1][1]
+        pinned = None
         try:
             with capture_guard.unsafe_host_op():
-                pinned = torch.empty(off, dtype=torch.uint8,
-                                     pin_memory=True)
+                if p_off:
+                    pinned = torch.empty(p_off, dtype=torch.uint8,
+                                         pin_memory=True)
+                host = _ArenaHost(
+                    off, pinned, [tuple(s) for s in spans],
+                    np.concatenate([table.view(np.uint8),
+                                    tile_start.view(np.uint8)]),
+                    len(table), int(tile_start[-1]))
+                if len(table):
+                    host.table_on(torch, self.device)
         except RuntimeError:
             log.warning("pinned transform-arena alloc failed; later "
                         "models will re-transform")
             return
-        for (key, o, nb, dt, shape), (_k, t) in zip(entries, items):
-            pinned[o:o + nb].view(dt)[:t.numel()].copy_(
-                t.reshape(-1), non_blocking=False)
-        _put_transform_arena(self.plan, self.dtype, entries, pinned)
+        for (key, _o, nb, dt, shape), (_k, t) in zip(entries, items):
+            po = pinned_at.get(key)
+            if po is not None:
+                pinned[po:po + nb].view(dt)[:t.numel()].copy_(
+                    t.reshape(-1), non_blocking=False)
+        _put_transform_arena(self.plan, self.dtype, entries, host)
 
     def try_restore_transforms(self) -> bool:
-        """One DMA restore of the transformed weights from the plan's
-        pinned arena (replaces the per-layer GPU transforms on repeat
-        cold loads of the same content)."""
-        torch, _ = _load_backend()
+        """Fill a device arena with the transformed weights on a repeat
+        cold load of the same content: one launch of the weight-layout
+        kernel over the master blob this load uploaded (stream order puts
+        it after the blob DMA), plus a DMA of the plan's pinned remainder
+        where it has one. No per-layer transform compute."""
+        torch, ext = _load_backend()
         got = _get_transform_arena(self.plan, self.dtype)
         if got is None:
             return False
-        entries, pinned = got
-        dev_arena = torch.empty(pinned.numel(), dtype=torch.uint8,
+        entries, host = got
+        dev_arena = torch.empty(host.total, dtype=torch.uint8,
                                 device=self.device)
         up = _get_upload_stream(torch, self.device)
         with capture_guard.unsafe_host_op():
+            table = host.table_on(torch, self.device) \
+                if host.n_entries else None
             with torch.cuda.stream(up):
-                dev_arena.copy_(pinned, non_blocking=True)
+                for a_off, p_off, n in host.spans:
+                    dev_arena[a_off:a_off + n].copy_(
+                        host.pinned[p_off:p_off + n], non_blocking=True)
+                if table is not None:
+                    ext.weight_layout(
+                        self._weight_blob.data_ptr(), dev_arena.data_ptr(),
+                        table.data_ptr(), host.n_entries,
+                        table.data_ptr() + host.n_entries *
+                        LAYOUT_ENTRY_DTYPE.itemsize, host.total_tiles)
+        # the kernel reads the table until the guarded synchronize in
+        # __init__; the plan's cache may drop it before that
+        self._layout_table = table
+        self.restored_by_kernel = table is not None
         self._arena_dev = dev_arena
         # LAZY views: region_bases() computes pointers straight from
         # the entry offsets; tensor views materialize only if someone
