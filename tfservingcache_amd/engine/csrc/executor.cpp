@@ -16,6 +16,7 @@
 
 #include <cstdint>
 #include <stdexcept>
+#include <tuple>
 #include <vector>
 
 #include "kernels.h"
@@ -562,8 +563,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             return std::unique_ptr<ExecPlan>(t.instantiate(ws, bases));
           });
 
-  // one launch on the current stream (engine/gpu.py
-  // try_restore_transforms); pointers are device addresses
+  // one layout launch on the current stream, on its own (the engine's
+  // repeat load goes through restore_weights below); pointers are device
+  // addresses
   mod.def("weight_layout",
           [](uintptr_t blob, uintptr_t arena, uintptr_t table, int n_entries,
              uintptr_t tile_start, int total_tiles) {
@@ -578,6 +580,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
               throw std::runtime_error(
                   std::string("weight_layout launch failed: ") +
                   hipGetErrorString(e));
+          },
+          py::call_guard<py::gil_scoped_release>());
+
+  // a repeat load's uploads, layout launch and one blocking sync on the
+  // given stream, GIL released (engine/gpu.py GpuModel._restore; see
+  // kernels.h restore_weights). Addresses as integers; spans are
+  // (arena offset, pinned offset, nbytes)
+  mod.def("restore_weights",
+          [](uintptr_t stream, uintptr_t blob_dev, uintptr_t blob_pinned,
+             int64_t blob_bytes, uintptr_t arena_dev, int64_t arena_bytes,
+             uintptr_t arena_pinned, int64_t pinned_bytes,
+             const std::vector<std::tuple<int64_t, int64_t, int64_t>>& spans,
+             uintptr_t table, int n_entries, uintptr_t tile_start,
+             int total_tiles) {
+            std::vector<tfsc::RestoreSpan> sp;
+            sp.reserve(spans.size());
+            for (const auto& t : spans)
+              sp.push_back({std::get<0>(t), std::get<1>(t), std::get<2>(t)});
+            tfsc::restore_weights(
+                reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<ushort*>(blob_dev),
+                reinterpret_cast<const ushort*>(blob_pinned), blob_bytes,
+                reinterpret_cast<uint8_t*>(arena_dev), arena_bytes,
+                reinterpret_cast<const uint8_t*>(arena_pinned), pinned_bytes,
+                sp, reinterpret_cast<const tfsc::LayoutEntry*>(table),
+                n_entries, reinterpret_cast<const int*>(tile_start),
+                total_tiles);
           },
           py::call_guard<py::gil_scoped_release>());
 

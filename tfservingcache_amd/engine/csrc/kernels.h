@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <vector>
 
 namespace tfsc {
 
@@ -161,6 +162,30 @@ struct LayoutEntry {
 void launch_weight_layout(hipStream_t s, const ushort* blob, uint8_t* arena,
                           const LayoutEntry* table_dev, int n_entries,
                           const int* tile_start_dev, int total_tiles);
+
+// One contiguous run of arena bytes a repeat load copies from the plan's
+// pinned remainder (int weights, fp8 bytes and scales).
+struct RestoreSpan {
+  int64_t arena_off, pinned_off, nbytes;
+};
+// A repeat cold load's whole upload on stream s, ended by one blocking
+// hipStreamSynchronize(s): blob_bytes from blob_pinned to blob_dev (0:
+// the blob is on the device already), every span from arena_pinned to
+// arena_dev, then the layout launch above when n_entries > 0. Host
+// pointers are pinned memory. Everything that can be checked on the host
+// is checked before the first enqueue, and a failed check throws with
+// nothing enqueued: a negative size, a null pointer that the sizes say is
+// used, a span outside [0, arena_bytes) or [0, pinned_bytes),
+// total_tiles < n_entries. The table is trusted as in
+// launch_weight_layout. Every HIP return code is checked; on a failure
+// after the first enqueue the stream is synchronised before the throw.
+void restore_weights(hipStream_t s, ushort* blob_dev,
+                     const ushort* blob_pinned, int64_t blob_bytes,
+                     uint8_t* arena_dev, int64_t arena_bytes,
+                     const uint8_t* arena_pinned, int64_t pinned_bytes,
+                     const std::vector<RestoreSpan>& spans,
+                     const LayoutEntry* table_dev, int n_entries,
+                     const int* tile_start_dev, int total_tiles);
 
 // GEMM: C[M,N] = act(A[M,K] @ B[K,N] + bias [+ residual]).
 // A row-major bf16, B row-major bf16 (pre-transposed at load if the graph

@@ -16,6 +16,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace tfsc {
 
@@ -133,6 +134,80 @@ void launch_weight_layout(hipStream_t s, const ushort* blob, uint8_t* arena,
   hipLaunchKernelGGL(k_weight_layout, dim3(total_tiles), dim3(WL_TPB), 0, s,
                      blob, arena, table_dev, n_entries, tile_start_dev,
                      total_tiles);
+}
+
+namespace {
+
+void wl_check(hipError_t e, hipStream_t s, const char* what) {
+  if (e == hipSuccess) return;
+  // what was enqueued before the failure still reads the caller's
+  // buffers: let it finish before the caller can free them
+  (void)hipStreamSynchronize(s);
+  throw std::runtime_error(std::string("restore_weights: ") + what + ": " +
+                           hipGetErrorString(e));
+}
+
+// [off, off + n) inside [0, size), without overflow
+bool wl_inside(int64_t off, int64_t n, int64_t size) {
+  return off >= 0 && n >= 0 && off <= size && n <= size - off;
+}
+
+}  // namespace
+
+void restore_weights(hipStream_t s, ushort* blob_dev,
+                     const ushort* blob_pinned, int64_t blob_bytes,
+                     uint8_t* arena_dev, int64_t arena_bytes,
+                     const uint8_t* arena_pinned, int64_t pinned_bytes,
+                     const std::vector<RestoreSpan>& spans,
+                     const LayoutEntry* table_dev, int n_entries,
+                     const int* tile_start_dev, int total_tiles) {
+  // every check comes before the first enqueue
+  if (blob_bytes < 0 || arena_bytes < 0 || pinned_bytes < 0)
+    throw std::runtime_error("restore_weights: negative size");
+  if (blob_bytes > 0 && (!blob_dev || !blob_pinned))
+    throw std::runtime_error("restore_weights: null blob pointer");
+  if (arena_bytes > 0 && !arena_dev)
+    throw std::runtime_error("restore_weights: null arena pointer");
+  if (!spans.empty() && (!arena_dev || !arena_pinned))
+    throw std::runtime_error("restore_weights: spans without an arena");
+  for (const RestoreSpan& sp : spans) {
+    if (sp.nbytes < 0)
+      throw std::runtime_error("restore_weights: negative span size");
+    if (!wl_inside(sp.arena_off, sp.nbytes, arena_bytes))
+      throw std::runtime_error("restore_weights: span outside the arena");
+    if (!wl_inside(sp.pinned_off, sp.nbytes, pinned_bytes))
+      throw std::runtime_error(
+          "restore_weights: span outside the pinned remainder");
+  }
+  if (n_entries < 0 || total_tiles < n_entries)
+    throw std::runtime_error(
+        "restore_weights: " + std::to_string(n_entries) + " entries, " +
+        std::to_string(total_tiles) + " tiles");
+  if (n_entries > 0 && (!blob_dev || !arena_dev || !table_dev ||
+                        !tile_start_dev))
+    throw std::runtime_error("restore_weights: null layout pointer");
+
+  bool any = false;
+  if (blob_bytes > 0) {
+    wl_check(hipMemcpyAsync(blob_dev, blob_pinned, (size_t)blob_bytes,
+                            hipMemcpyHostToDevice, s), s, "blob copy");
+    any = true;
+  }
+  for (const RestoreSpan& sp : spans) {
+    if (sp.nbytes == 0) continue;
+    wl_check(hipMemcpyAsync(arena_dev + sp.arena_off,
+                            arena_pinned + sp.pinned_off, (size_t)sp.nbytes,
+                            hipMemcpyHostToDevice, s), s, "span copy");
+    any = true;
+  }
+  if (n_entries > 0) {
+    // stream order puts the launch after the blob copy it reads
+    launch_weight_layout(s, blob_dev, arena_dev, table_dev, n_entries,
+                         tile_start_dev, total_tiles);
+    wl_check(hipGetLastError(), s, "layout launch");
+    any = true;
+  }
+  if (any) wl_check(hipStreamSynchronize(s), s, "synchronize");
 }
 
 }  // namespace tfsc

@@ -23,6 +23,7 @@ extension's K_GEMM); the numeric enum lives in csrc/executor.cpp only.
 """
 from __future__ import annotations
 
+from bisect import bisect_right
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -200,6 +201,70 @@ def blob_layout(plan: Plan) -> BlobLayout:
     return BlobLayout(slots, total, int_idx)
 
 
+@dataclass
+class LiveBlobLayout(BlobLayout):
+    """blob_layout restricted to the float weights some kernel can read,
+    in the same order and with the same slot padding. Call emission keeps
+    addressing the full layout; full_starts / compact_starts (element
+    offsets of the live slots, ascending, index for index) carry an
+    offset of one into the other."""
+    full_total: int
+    full_starts: List[int]
+    compact_starts: List[int]
+
+    def compact_byte_offset(self, full_byte_off: int) -> int:
+        """The compact-blob byte offset of a full-blob byte offset. An
+        offset into the middle of a slot keeps its distance from the slot
+        start. KeyError for an offset outside every live slot."""
+        i = bisect_right(self.full_starts, full_byte_off // 2) - 1
+        if i >= 0:
+            d = full_byte_off - self.full_starts[i] * 2
+            end = self.compact_starts[i + 1] if i + 1 < len(
+                self.compact_starts) else self.total
+            # d == 0: the start of an empty slot is still its start
+            if d == 0 or d < (end - self.compact_starts[i]) * 2:
+                return self.compact_starts[i] * 2 + d
+        raise KeyError(f"blob offset {full_byte_off} is in no live slot")
+
+
+def live_weights(plan: Plan) -> set:
+    """Indices of the tensors a kernel can read as a weight: every input
+    of an op and every signature output, and the root of its alias chain.
+    What the planner folded away (unfolded conv filters, BatchNorm
+    vectors) stays in plan.tensors but is in no op's inputs."""
+    live = set()
+    for op in plan.ops:
+        live.update(op.inputs)
+    live.update(plan.sig_outputs.values())
+    for i in list(live):
+        r, seen = i, 0
+        while plan.tensors[r].alias_of is not None and seen < 16:
+            r = plan.tensors[r].alias_of
+            seen += 1
+        live.add(r)
+    return live
+
+
+def live_blob_layout(plan: Plan) -> LiveBlobLayout:
+    """The layout the device blob and its pinned host copy are given
+    (engine/gpu.py). Integer weights are all kept: they are few."""
+    full = blob_layout(plan)
+    live = live_weights(plan)
+    slots: Dict[int, Tuple[int, int]] = {}
+    full_starts: List[int] = []
+    compact_starts: List[int] = []
+    total = 0
+    for idx, (off, n) in full.slots.items():     # ascending offsets
+        if idx not in live:
+            continue
+        slots[idx] = (total, n)
+        full_starts.append(off)
+        compact_starts.append(total)
+        total += _pad128(n)
+    return LiveBlobLayout(slots, total, full.int_idx, full.total,
+                          full_starts, compact_starts)
+
+
 # One transform-arena region as a padded 2-D transpose of a blob slot:
 # csrc/kernels.h LayoutEntry, field for field (40 bytes, no padding).
 LAYOUT_ENTRY_DTYPE = np.dtype([
@@ -208,10 +273,13 @@ LAYOUT_ENTRY_DTYPE = np.dtype([
 LAYOUT_TILE = 64
 
 
-def _layout_entry(plan: Plan, layout: BlobLayout, key: tuple):
+def _layout_entry(plan: Plan, key: tuple, layout: BlobLayout = None):
     """(src_off, rin, cin, c_src, c_dst, transpose, kp, dst_rows) of the
     region `key` when it is a re-layout of a blob slot (the "gw" and "cw"
-    regions of engine/gpu.py), else None."""
+    regions of engine/gpu.py), else None. src_off is in the coordinates
+    of `layout` (default: blob_layout(plan))."""
+    if layout is None:
+        layout = blob_layout(plan)
     if key[0] not in ("gw", "cw") or key[1] not in layout.slots:
         return None
     shape = tuple(plan.tensors[key[1]].weight.shape)
@@ -240,7 +308,7 @@ def _layout_entry(plan: Plan, layout: BlobLayout, key: tuple):
     return ent
 
 
-def weight_layout_table(plan: Plan, entries):
+def weight_layout_table(plan: Plan, entries, layout: BlobLayout = None):
     """The descriptor table of ops/weight_layout.hip for a transform
     arena whose regions are `entries` [(key, byte offset, nbytes, ...)]:
     (table, tile_start, covered). table is a LAYOUT_ENTRY_DTYPE array with
@@ -248,12 +316,15 @@ def weight_layout_table(plan: Plan, entries):
     (conv_weight, conv_weight_cpad, gemm_weight), tile_start [n + 1] int32
     the prefix sum of their 64x64 destination tiles, covered the set of
     their keys. Regions outside it (int weights, fp8 bytes and scales)
-    stay a host copy. Plan-deterministic: shapes and blob_layout only."""
-    layout = blob_layout(plan)
+    stay a host copy. Plan-deterministic: shapes and `layout` only, which
+    defaults to blob_layout(plan); with live_blob_layout(plan) passed in,
+    src_off addresses the compact blob."""
+    if layout is None:
+        layout = blob_layout(plan)
     rows, starts, covered = [], [0], set()
     for e in entries:
         key, off, nb = tuple(e[0]), e[1], e[2]
-        ent = _layout_entry(plan, layout, key)
+        ent = _layout_entry(plan, key, layout)
         if ent is None or ent[7] * ent[6] * 2 != nb:
             continue
         rows.append((ent[0], off) + ent[1:7])

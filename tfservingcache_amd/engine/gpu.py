@@ -4,9 +4,10 @@ What kernels a plan runs, on which buffers, is decided without a GPU in
 engine/emit.py: a call template per (plan, batch bucket, dtype) whose
 pointers are (region key, offset) descriptors. This module gives the
 template memory (all ahead of the hot path):
-  * weights: one bf16 master blob in the layout emit.blob_layout fixes,
-    plus layout transforms keyed as the template names them — GEMM/conv
-    weights pre-transposed to [N][K] bf16 with K zero-padded to a
+  * weights: one bf16 master blob holding the weights kernels can read
+    (emit.live_blob_layout; a template addresses emit.blob_layout, and
+    _call_template carries its blob offsets over), plus layout
+    transforms keyed as the template names them — GEMM/conv weights pre-transposed to [N][K] bf16 with K zero-padded to a
     multiple of 64 so both MFMA fragments read contiguously along K
     (see csrc/ops/gemm.hip), fp8 GEMM weights with row scales — computed
     on first use, or laid out from the blob by ops/weight_layout.hip on
@@ -33,7 +34,7 @@ import warnings
 import numpy as np
 
 from .emit import (LAYOUT_ENTRY_DTYPE, WS, _pad64, _pad128, _pad256b,
-                   blob_layout, build_template, check_layout_table,
+                   build_template, check_layout_table, live_blob_layout,
                    weight_layout_table)
 from .planner import Plan, is_sym, resolve_dim
 
@@ -187,7 +188,7 @@ capture_guard = _CaptureGuard()
 # Plans are content-deduplicated (engine/model.py inode-keyed plan
 # cache), so models sharing a SavedModel's bytes share a Plan — their
 # cold loads skip the CPU f32->bf16 convert and become one DMA.
-# Bounded: ~51 MB pinned per ResNet-50-sized plan.
+# Bounded: ~51 MB pinned per ResNet-50-sized plan (live weights only).
 _BLOB_CACHE_CAP = 4
 _blob_cache_lock = threading.Lock()
 _blob_cache: Dict[int, tuple] = {}       # id(plan) -> (plan, blob)
@@ -417,15 +418,45 @@ def _put_transform_arena(plan, dtype: str, entries, pinned) -> None:
             _transform_arenas.pop(old, None)
 
 
-def _call_template(ext, tmpl):
+_live_layouts: Dict[int, tuple] = {}         # id(plan) -> (plan, layout)
+
+
+def _live_layout(plan):
+    """emit.live_blob_layout(plan), computed once per plan: a walk over
+    every op and tensor is a third of a millisecond of Python on a
+    ResNet-50, and every cold load needs the layout."""
+    with _tmpl_lock:
+        ent = _live_layouts.get(id(plan))
+        if ent is not None and ent[0] is plan:
+            return ent[1]
+    layout = live_blob_layout(plan)
+    with _tmpl_lock:
+        _live_layouts[id(plan)] = (plan, layout)
+        while len(_live_layouts) > _TMPL_CAP:
+            _live_layouts.pop(next(iter(_live_layouts)))
+    return layout
+
+
+def _call_template(ext, tmpl, layout):
     """The C++ form of a template's calls: kinds by the extension's
     K_* value, pointers as (0, off) workspace | (1, region index, off)
-    | (2,) null."""
+    | (2,) null. The template addresses the blob by emit.blob_layout;
+    the device blob holds the live slots only (`layout`, the plan's
+    live_blob_layout), so blob offsets are rewritten here, once per
+    (plan, bucket, dtype)."""
     index = {k: i for i, k in enumerate(tmpl.region_keys)}
+    blob = index.get(("blob",))
+
+    def region(d):
+        i = index[d[0]]
+        if i == blob:
+            return (1, i, layout.compact_byte_offset(d[1]))
+        return (1, i, d[1])
+
     return ext.CallTemplate([
         (getattr(ext, "K_" + kind),
          [(2,) if d is None else (0, d[1]) if d[0] == WS
-          else (1, index[d[0]], d[1]) for d in descs],
+          else region(d) for d in descs],
          ints, floats)
         for kind, descs, ints, floats in tmpl.calls])
 
@@ -448,7 +479,7 @@ class ExecContext:
         cached = _get_ctx_template(plan, batch, gm.dtype)
         if cached is None:
             tmpl = build_template(plan, batch, gm.dtype)
-            ctmpl = _call_template(ext, tmpl)
+            ctmpl = _call_template(ext, tmpl, _live_layout(plan))
         else:
             tmpl, ctmpl = cached
         self.shapes = tmpl.shapes
@@ -636,156 +667,197 @@ class GpuModel:
         import os as _os
         import time as _time
         t0 = _time.monotonic()
-        self._upload_pending = False
         # whether this load's arena came from the weight-layout kernel
         self.restored_by_kernel = False
         with torch.cuda.device(device):
-            self._upload_weights()
-            restored = self.try_restore_transforms()
-            if self._upload_pending or restored:
-                # one sync covers the async work on the shared upload
-                # stream (master blob DMA, then the arena's layout
-                # kernel and remainder DMA). MUST be
-                # guard-serialized: a stream sync concurrent with
-                # another thread's capture invalidates the capture (the
-                # 100-step soak reproduced hipErrorStreamCapture*
-                # within seconds when this ran unguarded)
-                with capture_guard.unsafe_host_op():
-                    _get_upload_stream(torch, device).synchronize()
+            restored = self._upload_weights()
         if _os.environ.get("TFSC_LOAD_TIMING"):
             log.warning("upload_weights %.1fms (cached_blob=%s "
                         "arena=%s)", (_time.monotonic() - t0) * 1e3,
                         _blob_cache_get(plan) is not None, restored)
 
     # -- weights -----------------------------------------------------------
-    def _upload_weights(self) -> None:
-        """One coalesced H2D for all float weights: each is converted to
-        bf16 into a single pinned buffer (vectorized CPU convert), then
-        ONE DMA moves the model; per-tensor views slice the device blob.
-        (~270 individual .to(device) calls cost 60-130 ms per ResNet-50
-        cold load; this path is ~10 ms + one 100 MB transfer.)"""
+    def _upload_weights(self) -> bool:
+        """One coalesced H2D for the float weights kernels can read
+        (emit.live_blob_layout; what the planner folded away is never
+        uploaded): each is converted to bf16 into a single pinned buffer
+        (vectorized CPU convert), then ONE DMA moves the model;
+        per-tensor views slice the device blob. (~270 individual
+        .to(device) calls cost 60-130 ms per ResNet-50 cold load; this
+        path is ~10 ms + one 50 MB transfer.) A repeat load of the plan
+        finds the converted blob pinned and is one native call
+        (_restore). Returns whether a transform arena was restored."""
         torch, _ = _load_backend()
-        # the same layout call emission addresses the blob by
-        layout = blob_layout(self.plan)
+        layout = _live_layout(self.plan)
         tensors = self.plan.tensors
         self._int_idx = layout.int_idx
-        for idx in layout.int_idx:
-            self._weights[idx] = torch.from_numpy(np.ascontiguousarray(
-                tensors[idx].weight.astype(np.int32))).to(self.device)
+        arena = _get_transform_arena(self.plan, self.dtype)
+        if arena is None:
+            # (a restored arena holds the int weights)
+            for idx in layout.int_idx:
+                self._weights[idx] = torch.from_numpy(np.ascontiguousarray(
+                    tensors[idx].weight.astype(np.int32))).to(self.device)
         float_ws = [(idx, tensors[idx].weight, off, n)
                     for idx, (off, n) in layout.slots.items()]
         total = layout.total
         if not float_ws:
-            return
-        import os as _os
+            return self._restore(torch, None, arena, None)
         import time as _time
-        timing = _os.environ.get("TFSC_LOAD_TIMING")
         ta = _time.monotonic()
         blob = torch.empty(total, dtype=torch.bfloat16, device=self.device)
         tb = _time.monotonic()
         cached = _blob_cache_get(self.plan)
-        conv_held = False
-        conv_lock = None
+        if cached is not None and cached.numel() != total:
+            cached = None
         if cached is None:
             # single-flight the convert; a second concurrent first-load
             # of the same content waits and takes the cached blob
             conv_lock = _convert_lock(self.plan)
-            conv_lock.acquire()
-            conv_held = True
-            cached = _blob_cache_get(self.plan)
-            if cached is not None:
-                conv_lock.release()
-                conv_held = False
-        try:
-            self._upload_blob(torch, blob, cached, total, float_ws,
-                              timing, ta, tb)
-        finally:
-            if conv_held:
-                conv_lock.release()
-
-    def _upload_blob(self, torch, blob, cached, total, float_ws,
-                     timing, ta, tb):
-        import time as _time
-        if cached is not None and cached.numel() == total:
-            # converted blob already pinned in CPU RAM: ONE DMA on the
-            # dedicated upload stream, guard-serialized against captures
-            # (running it unguarded produced
-            # hipErrorStreamCaptureInvalidated under the full headline
-            # workload; the guard's writer preference keeps the wait to
-            # the captures already in flight, a few ms)
-            up = _get_upload_stream(torch, self.device)
-            tc = _time.monotonic()
-            with capture_guard.unsafe_host_op():
-                td = _time.monotonic()
-                with torch.cuda.stream(up):
-                    blob.copy_(cached, non_blocking=True)
-                te = _time.monotonic()
-                up.synchronize()
-            if timing:
-                tf_ = _time.monotonic()
-                log.warning(
-                    "upload phases: alloc=%.1f guard=%.1f copy=%.1f "
-                    "sync=%.1f ms", (tb - ta) * 1e3, (td - tc) * 1e3,
-                    (te - td) * 1e3, (tf_ - te) * 1e3)
-        else:
-            # stage through a SHARED reusable pinned buffer: per-load
-            # pinned allocation (page-locking ~100 MB) costs more than
-            # the copy and thrashes badly under LRU churn. The converted
-            # result is ALSO written to a cacheable pinned blob so the
-            # next load of this plan skips the CPU convert entirely.
-            cpu_blob = None
-            try:
-                with capture_guard.unsafe_host_op():
-                    cpu_blob = torch.empty(total, dtype=torch.bfloat16,
-                                           pin_memory=True)
-            except RuntimeError:
-                log.warning("pinned weight-blob allocation failed; "
-                            "skipping the converted-weight cache")
-            # the convert's flush() does DEVICE-WIDE synchronizes —
-            # unguarded, those poison any concurrent hipGraph capture
-            # (reproduced by the 2-rank-on-one-GPU dry run), so the
-            # whole staging loop is an unsafe host op. It runs once per
-            # plan content (single-flighted above).
-            with capture_guard.unsafe_host_op(), _staging_lock:
-                stage = _get_staging(torch)
-                cap = stage.numel()
-                batch_items = []        # (stage_off, blob_off, n)
-                stage_off = 0
-
-                def flush():
-                    nonlocal stage_off
-                    for s_off, b_off, n_ in batch_items:
-                        blob[b_off:b_off + n_].copy_(
-                            stage[s_off:s_off + n_], non_blocking=True)
-                    torch.cuda.synchronize(self.device)
-                    batch_items.clear()
-                    stage_off = 0
-
-                for _idx, w, off, n in float_ws:
-                    src = torch.from_numpy(np.ascontiguousarray(
-                        np.asarray(w, dtype=np.float32))).view(-1)
-                    done = 0
-                    while done < n:
-                        if stage_off >= cap:
-                            flush()
-                        take = min(n - done, cap - stage_off)
-                        stage[stage_off:stage_off + take].copy_(
-                            src[done:done + take])  # CPU f32->bf16
-                        if cpu_blob is not None:
-                            cpu_blob[off + done:off + done + take].copy_(
-                                stage[stage_off:stage_off + take])
-                        batch_items.append((stage_off, off + done, take))
-                        stage_off += take
-                        done += take
-                flush()
-            if cpu_blob is not None:
-                _blob_cache_put(self.plan, cpu_blob)
+            with conv_lock:
+                cached = _blob_cache_get(self.plan)
+                if cached is not None and cached.numel() != total:
+                    cached = None
+                if cached is None:
+                    self._convert_blob(torch, blob, total, float_ws)
+                    cached = False      # the device blob is filled
         self._weight_blob = blob              # keep the allocation alive
         # LAZY views: ~270 torch view creations per cold load cost
         # milliseconds; master_weight materializes on demand (a context
         # addresses the blob by offset and needs no view)
         self._blob_slots = {idx: (off, n, tuple(w.shape))
                             for idx, w, off, n in float_ws}
+        return self._restore(torch, cached if cached is not False else None,
+                             arena, tb - ta)
+
+    def _restore(self, torch, cached, arena, t_alloc) -> bool:
+        """What a load moves on the upload stream, as ONE native call in
+        ONE guarded section with ONE blocking sync: the DMA of the pinned
+        converted blob `cached` (None: the device blob is filled
+        already, or the plan has no float weights) and, when the plan
+        has a published transform `arena`, the fill of a device arena:
+        one launch of the weight-layout kernel over that blob (stream
+        order puts it after the blob DMA) plus a DMA of the plan's
+        pinned remainder where it has one. No per-layer transform
+        compute, no torch dispatch inside the section.
+
+        The section MUST be guard-serialized: the DMAs and the stream
+        sync, concurrent with another thread's capture, invalidate the
+        capture (hipErrorStreamCaptureInvalidated under the full
+        headline workload; the 100-step soak reproduced
+        hipErrorStreamCapture* within seconds when the sync ran
+        unguarded). The guard's writer preference keeps the wait to the
+        captures already in flight, a few ms."""
+        if cached is None and arena is None:
+            return False
+        import os as _os
+        import time as _time
+        _, ext = _load_backend()
+        blob = getattr(self, "_weight_blob", None)
+        entries, host = arena if arena is not None else (None, None)
+        dev_arena = None
+        if host is not None:
+            dev_arena = torch.empty(host.total, dtype=torch.uint8,
+                                    device=self.device)
+        up = _get_upload_stream(torch, self.device)
+        n_entries = host.n_entries if host is not None else 0
+        pinned = host.pinned if host is not None else None
+        tc = _time.monotonic()
+        with capture_guard.unsafe_host_op():
+            td = _time.monotonic()
+            table = host.table_on(torch, self.device) if n_entries else None
+            table_ptr = table.data_ptr() if n_entries else 0
+            ext.restore_weights(
+                up.cuda_stream,
+                blob.data_ptr() if blob is not None else 0,
+                cached.data_ptr() if cached is not None else 0,
+                cached.numel() * cached.element_size()
+                if cached is not None else 0,
+                dev_arena.data_ptr() if dev_arena is not None else 0,
+                host.total if host is not None else 0,
+                pinned.data_ptr() if pinned is not None else 0,
+                pinned.numel() if pinned is not None else 0,
+                host.spans if host is not None else [],
+                table_ptr, n_entries,
+                table_ptr + n_entries * LAYOUT_ENTRY_DTYPE.itemsize
+                if n_entries else 0,
+                host.total_tiles if n_entries else 0)
+        if _os.environ.get("TFSC_LOAD_TIMING"):
+            te = _time.monotonic()
+            log.warning(
+                "upload phases: alloc=%.1f guard=%.1f restore=%.1f ms",
+                (t_alloc or 0.0) * 1e3, (td - tc) * 1e3, (te - td) * 1e3)
+        if host is None:
+            return False
+        self.restored_by_kernel = n_entries > 0
+        self._arena_dev = dev_arena
+        # LAZY views: region_bases() computes pointers straight from
+        # the entry offsets; tensor views materialize only if someone
+        # asks an accessor for the transform itself. ~300 eager view
+        # creations per cold load were milliseconds of Python.
+        self._arena_entries = {tuple(e[0]): e for e in entries}
+        # int weights live in the arena from here on (master_weight
+        # reads _weights[idx]); they are few
+        for key, off, nb, dt, shape in entries:
+            if key[0] == "int":
+                self._weights[key[1]] = \
+                    dev_arena[off:off + nb].view(dt).view(shape)
+        return True
+
+    def _convert_blob(self, torch, blob, total, float_ws):
+        """A plan's first load: convert to bf16 and fill the device blob
+        and, for the loads after it, a cacheable pinned copy."""
+        # stage through a SHARED reusable pinned buffer: per-load
+        # pinned allocation (page-locking ~100 MB) costs more than
+        # the copy and thrashes badly under LRU churn. The converted
+        # result is ALSO written to a cacheable pinned blob so the
+        # next load of this plan skips the CPU convert entirely.
+        cpu_blob = None
+        try:
+            with capture_guard.unsafe_host_op():
+                cpu_blob = torch.empty(total, dtype=torch.bfloat16,
+                                       pin_memory=True)
+        except RuntimeError:
+            log.warning("pinned weight-blob allocation failed; "
+                        "skipping the converted-weight cache")
+        # the convert's flush() does DEVICE-WIDE synchronizes —
+        # unguarded, those poison any concurrent hipGraph capture
+        # (reproduced by the 2-rank-on-one-GPU dry run), so the
+        # whole staging loop is an unsafe host op. It runs once per
+        # plan content (single-flighted above).
+        with capture_guard.unsafe_host_op(), _staging_lock:
+            stage = _get_staging(torch)
+            cap = stage.numel()
+            batch_items = []        # (stage_off, blob_off, n)
+            stage_off = 0
+
+            def flush():
+                nonlocal stage_off
+                for s_off, b_off, n_ in batch_items:
+                    blob[b_off:b_off + n_].copy_(
+                        stage[s_off:s_off + n_], non_blocking=True)
+                torch.cuda.synchronize(self.device)
+                batch_items.clear()
+                stage_off = 0
+
+            for _idx, w, off, n in float_ws:
+                src = torch.from_numpy(np.ascontiguousarray(
+                    np.asarray(w, dtype=np.float32))).view(-1)
+                done = 0
+                while done < n:
+                    if stage_off >= cap:
+                        flush()
+                    take = min(n - done, cap - stage_off)
+                    stage[stage_off:stage_off + take].copy_(
+                        src[done:done + take])  # CPU f32->bf16
+                    if cpu_blob is not None:
+                        cpu_blob[off + done:off + done + take].copy_(
+                            stage[stage_off:stage_off + take])
+                    batch_items.append((stage_off, off + done, take))
+                    stage_off += take
+                    done += take
+            flush()
+        if cpu_blob is not None:
+            _blob_cache_put(self.plan, cpu_blob)
 
     def master_weight(self, idx: int):
         """bf16 master view of plan weight idx (blob slice or int
@@ -1001,9 +1073,11 @@ class GpuModel:
         covered = set()
         if gpu_layout_enabled() and \
                 getattr(self, "_weight_blob", None) is not None:
+            # the device blob is compact: so are the table's src_off
             table, tile_start, covered = weight_layout_table(
                 self.plan, [e for e in entries
-                            if e[3] == torch.bfloat16])
+                            if e[3] == torch.bfloat16],
+                layout=_live_layout(self.plan))
             check_layout_table(table, tile_start,
                                self._weight_blob.numel(), off)
         # contiguous runs of the regions that stay a host copy
@@ -1042,51 +1116,6 @@ class GpuModel:
                     t.reshape(-1), non_blocking=False)
         _put_transform_arena(self.plan, self.dtype, entries, host)
 
-    def try_restore_transforms(self) -> bool:
-        """Fill a device arena with the transformed weights on a repeat
-        cold load of the same content: one launch of the weight-layout
-        kernel over the master blob this load uploaded (stream order puts
-        it after the blob DMA), plus a DMA of the plan's pinned remainder
-        where it has one. No per-layer transform compute."""
-        torch, ext = _load_backend()
-        got = _get_transform_arena(self.plan, self.dtype)
-        if got is None:
-            return False
-        entries, host = got
-        dev_arena = torch.empty(host.total, dtype=torch.uint8,
-                                device=self.device)
-        up = _get_upload_stream(torch, self.device)
-        with capture_guard.unsafe_host_op():
-            table = host.table_on(torch, self.device) \
-                if host.n_entries else None
-            with torch.cuda.stream(up):
-                for a_off, p_off, n in host.spans:
-                    dev_arena[a_off:a_off + n].copy_(
-                        host.pinned[p_off:p_off + n], non_blocking=True)
-                if table is not None:
-                    ext.weight_layout(
-                        self._weight_blob.data_ptr(), dev_arena.data_ptr(),
-                        table.data_ptr(), host.n_entries,
-                        table.data_ptr() + host.n_entries *
-                        LAYOUT_ENTRY_DTYPE.itemsize, host.total_tiles)
-        # the kernel reads the table until the guarded synchronize in
-        # __init__; the plan's cache may drop it before that
-        self._layout_table = table
-        self.restored_by_kernel = table is not None
-        self._arena_dev = dev_arena
-        # LAZY views: region_bases() computes pointers straight from
-        # the entry offsets; tensor views materialize only if someone
-        # asks an accessor for the transform itself. ~300 eager view
-        # creations per cold load were milliseconds of Python.
-        self._arena_entries = {tuple(e[0]): e for e in entries}
-        # int weights live in the arena from here on (master_weight
-        # reads _weights[idx]); they are few
-        for key, off, nb, dt, shape in entries:
-            if key[0] == "int":
-                self._weights[key[1]] = \
-                    dev_arena[off:off + nb].view(dt).view(shape)
-        return True
-
     def _arena_view(self, key: tuple):
         ent = getattr(self, "_arena_entries", {}).get(tuple(key))
         if ent is None or self._arena_dev is None:
@@ -1102,10 +1131,15 @@ class GpuModel:
         arena = getattr(self, "_arena_dev", None)
         if arena is not None:
             total += arena.numel() * arena.element_size()
+        # views of the blob (master_weight) and of the arena (a restored
+        # load's int weights and transforms) are counted above
+        own = {t.untyped_storage().data_ptr()
+               for t in (blob, arena) if t is not None}
         for d in (self._weights, self._gemm_weights, self._conv_weights):
             for wt in d.values():
                 if wt is not None and getattr(wt, "untyped_storage",
-                                              None) is not None:
+                                              None) is not None and \
+                        wt.untyped_storage().data_ptr() not in own:
                     total += wt.numel() * wt.element_size()
         return total
 
